@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py — TokenPacker projector throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]          # N=1; N>1 with no launcher around it: bench.py starts its own
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
+                                                             # N=1; N>1 with no launcher around it: bench.py starts its own
                                                              # N ranks (torch.distributed.run on 127.0.0.1) and rank 0 prints
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
@@ -26,12 +27,15 @@ Other workloads (each prints the same one-line JSON):
           288 % N != 0), ONE all-gather of b_max-row slots, then the HD token assembly (tp_hd_assemble) reading the
           gathered buffer in place.
   --e2e   BASELINE configs[4], encode_images() end to end (N > 1: `python bench.py --e2e --gpus N` starts its own ranks like the
-          projector bench; the line also carries `reference_leg` / `vs_reference`: the same run with the reference's projector): random-init CLIP-ViT-L/14-336 forward (HF transformers on
+          projector bench; with --full the line also carries `split_ms`, `reference_leg` / `vs_reference`: the same run with the reference's projector): random-init CLIP-ViT-L/14-336 forward (HF transformers on
           PyTorch-ROCm — the producer, not our code) -> HIP projector on the four hidden-state slices (no torch.cat)
           -> Vicuna-7B-shaped prefill (32 Llama layers of GEMMs + SDPA on PyTorch-ROCm — the consumer, not our code),
           B=64 split over the ranks DDP-style; tokens/s plus the split into tower / projector / prefill time.
 
-Rank 0 prints ONE JSON line.  Besides the driver's contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run does only what the headline figure needs: it sets up, warms up (W steps), times
+EXACTLY K steps, writes the last timed step's outputs with ``--dump-outputs DIR`` and prints the line (metric, value, unit,
+ms_per_step, higher_is_better, dtype, config, whole_path; N>1: the multi_gpu block without its probes).  With ``--full`` the line
+also carries what takes measurements of its own:
   roofline     — dominant kernel = the first K/V layer GEMM (x_multi·[Wk0;Wv0]^T + GELU, 45 % of the path's FLOPs):
                  algorithmic FLOPs per launch / its average duration measured with HIP events recorded by the library
                  on the launch stream inside a real forward (tp_forward_staged), against the dense bf16 MFMA peak;
@@ -144,7 +148,18 @@ def parse_args():
                          "distribution over blocks of steps (timing.long_run); 0: off")
     ap.add_argument("--no-extras", action="store_true",
                     help="N=1: skip the eager PyTorch-ROCm baseline and the s=3 / s=4 / B=32 sweep that follow the timed region")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, measure everything else the line can carry (clocks, timing.long_run, "
+                         "stages_ms / roofline / memory_side, the N>1 forward-only / gather-only probes, pack_ms, the sweep, the eager "
+                         "and CPU baselines, the --e2e split and reference leg); --min-seconds, --no-extras, --no-cpu-baseline and "
+                         "--probe-other-gather act under --full.  Off (default): set up, warm up, time --steps steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, "
+                         "< 64 MB in all: a fixed, seeded sample of the rows of a larger output plus every row's sum)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def self_spawn(args) -> None:
@@ -160,6 +175,32 @@ def self_spawn(args) -> None:
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.exit(subprocess.run(cmd, env=env).returncode)
+
+
+DUMP_SAMPLE_BYTES = 56_000_000          # the sampled rows of every output together; the row sums come on top (< 64 MB in all)
+
+
+def dump_outputs(directory: str, outputs: dict, seed: int = 0) -> None:
+    """--dump-outputs: write each output tensor as ``<name>.npy`` so that two builds can be compared output for output.  An
+    output that fits its share of DUMP_SAMPLE_BYTES as float32 is written whole.  A larger one is viewed as rows of its last
+    dimension and written as ``<name>.npy`` = a fixed sample of those rows (a seeded permutation, sorted; float32),
+    ``<name>_rows.npy`` = the flat indices of the sampled rows (float64) and ``<name>_row_sum.npy`` = the float64 sum of EVERY
+    row, in the tensor's leading shape, so that no element goes unseen."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_SAMPLE_BYTES // max(len(outputs), 1)
+    for name, t in outputs.items():
+        t = t.detach()
+        if t.numel() * 4 <= share:
+            np.save(os.path.join(directory, f"{name}.npy"), t.float().cpu().numpy())
+            continue
+        lead, width = tuple(t.shape[:-1]), t.shape[-1]
+        rows = t.reshape(-1, width)
+        k = max(1, min(rows.shape[0], share // (width * 4)))
+        pick = torch.randperm(rows.shape[0], generator=torch.Generator().manual_seed(seed))[:k].sort().values
+        np.save(os.path.join(directory, f"{name}.npy"), rows[pick.to(rows.device)].float().cpu().numpy())
+        np.save(os.path.join(directory, f"{name}_rows.npy"), pick.double().numpy())
+        np.save(os.path.join(directory, f"{name}_row_sum.npy"), rows.double().sum(-1).reshape(lead).cpu().numpy())
 
 
 def make_device_inputs(B, dtype, layout, device, seed):
@@ -412,7 +453,7 @@ def run_e2e(args, world, rank, device, dtype, dist):
 
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
     use_reference = {"on": False}          # the reference leg (after the timed region): the reference's own projector + feature_select
-    eager_forward = _reference_op_sequence() if not args.no_extras else None
+    eager_forward = _reference_op_sequence() if args.full and not args.no_extras else None
 
     def step(timed=False):
         if timed:
@@ -448,27 +489,33 @@ def run_e2e(args, world, rank, device, dtype, dist):
         for _ in range(max(args.warmup, 1)):
             out = step()
         fence()
-        clocks["before"] = read_clocks(device) if rank == 0 else {}
+        if args.full:
+            clocks["before"] = read_clocks(device) if rank == 0 else {}
         t_start = time.perf_counter()
         for _ in range(args.steps):
             out = step()
-        if rank == 0:                        # while the last steps are still executing: the clocks of the loaded chip
+        if args.full and rank == 0:          # while the last steps are still executing: the clocks of the loaded chip
             clocks["during"] = read_clocks(device)
         fence()
         el = torch.tensor([time.perf_counter() - t_start], dtype=torch.float64, device=device)
-        clocks["after"] = read_clocks(device) if rank == 0 else {}
+        if args.full:
+            clocks["after"] = read_clocks(device) if rank == 0 else {}
         if world > 1:
             dist.all_reduce(el, op=dist.ReduceOp.MAX)
         return out, float(el.item())
 
     with torch.no_grad():
         y, elapsed = timed_region()               # (no collective on this path: every rank prefills its own samples)
-        step(timed=True)
-        torch.cuda.synchronize(device)
-        split = [ev[i].elapsed_time(ev[i + 1]) for i in range(3)]
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"prefill_hidden": y})
+        split = None
+        if args.full:
+            step(timed=True)
+            torch.cuda.synchronize(device)
+            split = [ev[i].elapsed_time(ev[i + 1]) for i in range(3)]
         # The reference leg — BASELINE configs[4] asks for tokens/s "vs reference": the SAME tower, prefill, inputs and protocol with
         # the reference's projector (its torch op sequence on PyTorch-ROCm eager, fed by its torch.cat feature_select) in place of
-        # the HIP one.  After the timed region, never inside it; skipped with --no-extras.
+        # the HIP one.  After the timed region, never inside it; --full only, skipped with --no-extras.
         ref_elapsed, ref_split, ref_err = 0.0, None, None
         if eager_forward is not None:
             try:
@@ -499,10 +546,11 @@ def run_e2e(args, world, rank, device, dtype, dist):
                                   f"tokens per sample",
                       "global_batch": args.e2e_batch, "per_gpu_batch": b, "parallelism": f"DDP-style batch shard x{world}, no collective",
                       "tokens_per_step": tokens},
-           "split_ms": {"tower": round(split[0], 3), "projector_hip": round(split[1], 3), "prefill": round(split[2], 3)},
-           "clocks": clocks,
            "note": "tower and prefill are PyTorch-ROCm library code around the path (producer / consumer), timed to place the "
                    "projector inside encode_images(); only projector_hip is this repository's kernels"}
+    if split is not None:
+        out["split_ms"] = {"tower": round(split[0], 3), "projector_hip": round(split[1], 3), "prefill": round(split[2], 3)}
+        out["clocks"] = clocks
     if ref_elapsed > 0:
         ref_value = tokens * args.steps / ref_elapsed
         out["reference_leg"] = {"value": round(ref_value, 1), "unit": "tokens/s", "ms_per_step": round(1e3 * ref_elapsed / args.steps, 3),
@@ -571,6 +619,8 @@ def run_sdma_leg(args, world) -> None:
            "--gather-depth", str(args.gather_depth), "--no-cpu-baseline", "--no-extras", "--min-seconds", "0"]
     if args.single_device:
         cmd.append("--single-device")
+    if args.full:
+        cmd.append("--full")
     if args.sync_gather:
         cmd.append("--sync-gather")
     for kv in args.tune:
@@ -782,15 +832,17 @@ def main():
         for _ in range(max(args.warmup, 1)):
             out = step()
         fence()
-        clocks["before"] = read_clocks(device) if rank == 0 else {}
+        if args.full:
+            clocks["before"] = read_clocks(device) if rank == 0 else {}
         t_start = time.perf_counter()
         for _ in range(args.steps):
             out = step()
-        if rank == 0:                        # while the last steps are still executing: the clocks of the loaded chip
+        if args.full and rank == 0:          # while the last steps are still executing: the clocks of the loaded chip
             clocks["during"] = read_clocks(device)
         fence()
         el = torch.tensor([time.perf_counter() - t_start], dtype=torch.float64, device=device)
-        clocks["after"] = read_clocks(device) if rank == 0 else {}
+        if args.full:
+            clocks["after"] = read_clocks(device) if rank == 0 else {}
         if use_dist:
             dist.all_reduce(el, op=dist.ReduceOp.MAX)
         return out, float(el.item())
@@ -801,11 +853,16 @@ def main():
         if transports:
             per_transport[cur["t"]] = elapsed
         chosen = cur["t"]
+        if args.dump_outputs and rank == 0:
+            # what the caller of the timed path receives: the (gathered) tokens, or the HD token sequences of every image
+            dump_outputs(args.dump_outputs, {"hd_tokens": torch.cat(list(y))} if args.hd else {"tokens": y})
+
+        # Everything from here to the line is --full only: the K-step region above is the headline figure.
 
         # The K steps above are the driver's; at 4 ms per step they are < 0.1 s of clock.  Keep stepping (same loop, same
         # fences) until --min-seconds have been measured, in blocks, so that the line also carries a distribution.
         long_run = None
-        if args.min_seconds > 0 and args.steps > 0 and not args.hd:
+        if args.full and args.min_seconds > 0 and not args.hd:
             per = max(elapsed / args.steps, 1e-6)
             blk = max(1, min(args.steps, int(0.05 / per) + 1))
             n_blk = int(min(200, max(5, args.min_seconds / (per * blk))))
@@ -834,7 +891,7 @@ def main():
         # launch stream (tp_forward_staged).  A few extra forwards after the timed region.
         n_prof = min(max(args.steps, 3), 10)
         stage_ms = [0.0] * _capi.TP_NUM_STAGES
-        for _ in range(n_prof if B > 0 else 0):
+        for _ in range(n_prof if B > 0 and args.full else 0):
             _, evs = model.forward_staged((x, xm))
             torch.cuda.synchronize(device)
             for i in range(_capi.TP_NUM_STAGES):
@@ -843,7 +900,7 @@ def main():
         # N>1 diagnostics, outside the timed region: the same shard without the gather (what DDP training sees) and
         # the gather alone on a fixed shard, so the scaling numbers can be split into compute and xGMI time
         extra = {}
-        if gather:
+        if gather and args.full:
             n_x = min(max(args.steps, 3), 10)
             y_loc = model((x, xm))
             fence()
@@ -922,10 +979,6 @@ def main():
 
     if rank == 0:
         fl_img = flops_per_image(s, D)
-        kv0_flops = 2.0 * B * 576 * 4096 * 2048                 # algorithmic FLOPs of the dominant launch ON THIS RANK
-        kv0_ms = stage_ms[1]
-        achieved = kv0_flops / (kv0_ms * 1e-3) / 1e12 if kv0_ms > 0 else 0.0
-        traffic, traffic_src = load_traffic(B, args.dtype, args.layout)
         unit_name = "HD crops (projector batch elements)" if args.hd else "images"
         out = {
             "metric": "projector images/sec",
@@ -955,57 +1008,63 @@ def main():
                            "algorithmic_gflop_per_image": round(fl_img / 1e9, 3),
                            "algorithmic_io_mb_per_image": round(bytes_per_image(s, D) / 1e6, 3),
                            "io_gbps": round(bytes_per_image(s, D) * total / (ms_per_step * 1e-3) / 1e9, 1)},
-            "roofline": {"kernel": "tp::gemm8_kernel<T, f16, STRIDED_A> 256x256x64 ping-pong (kv_layer0: x_multi·[Wk0;Wv0]^T + bias + GELU)",
-                         "bound": "mfma", "achieved": round(achieved, 1), "peak": MFMA_PEAK_TFLOPS,
-                         "unit": "TFLOP/s", "frac": round(achieved / MFMA_PEAK_TFLOPS, 4),
-                         "flops_per_launch": kv0_flops, "avg_launch_ms": round(kv0_ms, 4),
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "traffic_unit": "bytes/launch (rocprofv3 PMC, profiles/traffic.json)",
-                         "algorithmic_bytes": float(B * 576 * 4096 * 2 + 2048 * 4096 * 2 + B * 576 * 2048 * 2)},
-            "stages_ms": {n: round(v, 4) for n, v in zip(_capi.STAGE_NAMES, stage_ms)},
         }
-        # the store-heavy short-K launch over the launch that stores nothing: 0.8 - 0.9 normally, ~1.3 in the slow memory-side
-        # power state some boxes put a 32 ... 128-image forward in (profiles/r03u_mid_batch_anomaly.txt)
-        out["clocks"] = clocks
-        sclk = load_sustained_clock(B, args.dtype, args.layout)
-        if sclk:
-            # information beside `frac` (which stays achieved / 2.5 PFLOP/s): the same rate against the peak at the clock the power limit allows
-            out["roofline"]["at_sustained_clock"] = {"shader_clock_ghz": round(sclk, 3), "boost_clock_ghz": 2.4,
-                                                     "peak": round(MFMA_PEAK_TFLOPS * sclk / 2.4, 1),
-                                                     "frac": round(achieved / (MFMA_PEAK_TFLOPS * sclk / 2.4), 4),
-                                                     "source": "profiles/traffic.json (cycle counters of the PMC session over this launch); DESIGN.md 5.9 (b)"}
-        if stage_ms[2] > 0 and s == 2:
-            out["memory_side"] = {"mlp0_over_statistics": round(stage_ms[8] / stage_ms[2], 3),
-                                  "note": "mlp0_gelu / kv_layer2_stats of this rank's forward; ~0.85 normal, >= 1.2 = the node's slow memory-side power state"}
+        if args.full:
+            kv0_flops = 2.0 * B * 576 * 4096 * 2048                 # algorithmic FLOPs of the dominant launch ON THIS RANK
+            kv0_ms = stage_ms[1]
+            achieved = kv0_flops / (kv0_ms * 1e-3) / 1e12 if kv0_ms > 0 else 0.0
+            traffic, traffic_src = load_traffic(B, args.dtype, args.layout)
+            out["roofline"] = {"kernel": "tp::gemm8_kernel<T, f16, STRIDED_A> 256x256x64 ping-pong (kv_layer0: x_multi·[Wk0;Wv0]^T + bias + GELU)",
+                               "bound": "mfma", "achieved": round(achieved, 1), "peak": MFMA_PEAK_TFLOPS,
+                               "unit": "TFLOP/s", "frac": round(achieved / MFMA_PEAK_TFLOPS, 4),
+                               "flops_per_launch": kv0_flops, "avg_launch_ms": round(kv0_ms, 4),
+                               "traffic": traffic, "traffic_source": traffic_src,
+                               "traffic_unit": "bytes/launch (rocprofv3 PMC, profiles/traffic.json)",
+                               "algorithmic_bytes": float(B * 576 * 4096 * 2 + 2048 * 4096 * 2 + B * 576 * 2048 * 2)}
+            out["stages_ms"] = {n: round(v, 4) for n, v in zip(_capi.STAGE_NAMES, stage_ms)}
+            out["clocks"] = clocks
+            sclk = load_sustained_clock(B, args.dtype, args.layout)
+            if sclk:
+                # information beside `frac` (which stays achieved / 2.5 PFLOP/s): the same rate against the peak at the clock the power limit allows
+                out["roofline"]["at_sustained_clock"] = {"shader_clock_ghz": round(sclk, 3), "boost_clock_ghz": 2.4,
+                                                         "peak": round(MFMA_PEAK_TFLOPS * sclk / 2.4, 1),
+                                                         "frac": round(achieved / (MFMA_PEAK_TFLOPS * sclk / 2.4), 4),
+                                                         "source": "profiles/traffic.json (cycle counters of the PMC session over this launch); DESIGN.md 5.9 (b)"}
+            # the store-heavy short-K launch over the launch that stores nothing: 0.8 - 0.9 normally, ~1.3 in the slow memory-side
+            # power state some nodes put a 32 ... 128-image forward in (profiles/r03u_mid_batch_anomaly.txt)
+            if stage_ms[2] > 0 and s == 2:
+                out["memory_side"] = {"mlp0_over_statistics": round(stage_ms[8] / stage_ms[2], 3),
+                                      "note": "mlp0_gelu / kv_layer2_stats of this rank's forward; ~0.85 normal, >= 1.2 = the node's slow memory-side power state"}
         if gather:
             # max over ranks; gather_only moves (N-1)/N of [total, M, D] into every rank per step
             out["multi_gpu"] = {"forward_only_ms": round(float(t[1].item()), 4),
                                 "forward_only_images_per_s": round(total / (float(t[1].item()) * 1e-3), 1),
-                                "gather_only_ms": round(float(t[2].item()), 4),
-                                "collective": (f"DirectGather: {world - 1} hipMemcpyAsync (copy engines, no CU) per rank and step + sequence flags, "
-                                               f"depth {args.gather_depth}" if chosen == "sdma" else
-                                               f"{args.backend} all_gather_into_tensor over {world} ranks") + (" (ragged: b_max-row slots)" if ragged and chosen != "sdma" else ""),
-                                "gather": chosen if chosen else "rccl",
-                                "gather_requested": args.gather,
-                                "transports_timed_ms_per_step": {k: round(1e3 * v / args.steps, 4) for k, v in per_transport.items()},
-                                "sdma_self_test": "passed" if (dgather is not None and chosen == "sdma") else None,
-                                "sdma_flags_fine_grained": (dgather.flags_fine_grained if dgather is not None else None),
-                                "pipelined": bool((chosen == "rccl" and pipe is not None) or (chosen == "sdma" and not args.sync_gather)),
-                                "gather_bytes_received_per_rank": int((total - B) * M * D * 2),
-                                "ranks": dist.get_world_size(), "backend": dist.get_backend(), "rank_devices": rank_info,
-                                "collective_self_check": dict(COLLECTIVE_CHECK),
-                                "env": {k: os.environ.get(k) for k in ("NCCL_ALGO", "NCCL_PROTO", "NCCL_MIN_NCHANNELS", "NCCL_MAX_NCHANNELS",
-                                                                        "RCCL_MSCCL_ENABLE", "HSA_ENABLE_IPC_MODE_LEGACY", "HSA_ENABLE_SDMA")
-                                        if os.environ.get(k) is not None}}
+                                "gather_only_ms": round(float(t[2].item()), 4)} if args.full else {}
+            out["multi_gpu"].update({
+                    "collective": (f"DirectGather: {world - 1} hipMemcpyAsync (copy engines, no CU) per rank and step + sequence flags, "
+                                   f"depth {args.gather_depth}" if chosen == "sdma" else
+                                   f"{args.backend} all_gather_into_tensor over {world} ranks") + (" (ragged: b_max-row slots)" if ragged and chosen != "sdma" else ""),
+                    "gather": chosen if chosen else "rccl",
+                    "gather_requested": args.gather,
+                    "transports_timed_ms_per_step": {k: round(1e3 * v / args.steps, 4) for k, v in per_transport.items()},
+                    "sdma_self_test": "passed" if (dgather is not None and chosen == "sdma") else None,
+                    "sdma_flags_fine_grained": (dgather.flags_fine_grained if dgather is not None else None),
+                    "pipelined": bool((chosen == "rccl" and pipe is not None) or (chosen == "sdma" and not args.sync_gather)),
+                    "gather_bytes_received_per_rank": int((total - B) * M * D * 2),
+                    "ranks": dist.get_world_size(), "backend": dist.get_backend(), "rank_devices": rank_info,
+                    "collective_self_check": dict(COLLECTIVE_CHECK),
+                    "env": {k: os.environ.get(k) for k in ("NCCL_ALGO", "NCCL_PROTO", "NCCL_MIN_NCHANNELS", "NCCL_MAX_NCHANNELS",
+                                                            "RCCL_MSCCL_ENABLE", "HSA_ENABLE_IPC_MODE_LEGACY", "HSA_ENABLE_SDMA")
+                            if os.environ.get(k) is not None}})
             if "other_gather" in extra:
                 out["multi_gpu"]["other_gather"] = {"mode": extra["other_gather"]["mode"], "gather_only_ms": round(float(t[3].item()), 4)}
                 if float(t[4].item()) > 0:
                     out["multi_gpu"]["other_gather"]["pipelined_ms_per_step"] = round(float(t[4].item()), 4)
         if long_run is not None:
             out["timing"] = {"timed_region_s": round(elapsed, 4), "long_run": long_run}
-        if world == 1 and not args.no_extras and not args.hd:
+        if world == 1 and args.full and not args.no_extras and not args.hd:
             out.update(gpu_extras(args, model, x, xm, dtype, device, images_per_s))
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, s, D, args.cpu_threads)
         flush_c_stdio()
         print(json.dumps(out), flush=True)

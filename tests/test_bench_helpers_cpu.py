@@ -5,6 +5,7 @@ import os
 import sys
 
 import pytest
+import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -55,3 +56,38 @@ def test_broken_file_does_not_break_the_line(tmp_path, monkeypatch):
     traffic, src = bench.load_traffic(256, "bf16", "tower")
     assert traffic is None and "unreadable" in src
     assert bench.load_sustained_clock(256, "bf16", "tower") is None
+
+
+def test_plain_run_is_the_default_and_steps_must_be_positive(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse_args()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse_args()
+    assert a.full and a.dump_outputs == "d"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse_args()
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: a small output is written whole in float32; a larger one as a seeded sample of its rows (the same rows
+    every run), their flat indices and the float64 sum of every row, within the byte budget."""
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_BYTES", 2 * 1024 * 4 * 16)       # 16 rows of 1024 fp32 per output
+    g = torch.Generator().manual_seed(0)
+    small = torch.randn(2, 3, 8, generator=g).to(torch.bfloat16)
+    big = torch.randn(4, 50, 1024, generator=g).to(torch.bfloat16)
+    bench.dump_outputs(str(tmp_path / "a"), {"small": small, "big": big})
+    bench.dump_outputs(str(tmp_path / "b"), {"small": small, "big": big})
+    a = {f: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(a) == ["big.npy", "big_row_sum.npy", "big_rows.npy", "small.npy"]
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert np.array_equal(a["small.npy"], small.float().numpy())
+    rows = a["big_rows.npy"].astype(np.int64)
+    assert len(rows) == 16 and np.all(np.diff(rows) > 0) and rows.max() < 200
+    assert np.array_equal(a["big.npy"], big.reshape(-1, 1024).float().numpy()[rows])
+    assert a["big_row_sum.npy"].shape == (4, 50)
+    assert np.allclose(a["big_row_sum.npy"], big.double().sum(-1).numpy(), rtol=0, atol=1e-9)
+    for f, v in a.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / f)), f

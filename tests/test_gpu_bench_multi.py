@@ -22,7 +22,7 @@ def _free_port():
 def _run(extra, nproc=2, env=None, expect_rc=0):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", "3", "--warmup", "1",
-           "--backend", "gloo", "--single-device", "--no-cpu-baseline"] + extra
+           "--backend", "gloo", "--single-device", "--no-cpu-baseline", "--full"] + extra
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=dict(os.environ, **(env or {})))
     if expect_rc != 0:
         assert res.returncode != 0, res.stdout[-2000:]
@@ -75,7 +75,8 @@ def test_hd_line_ragged():
 def test_e2e_line_single_rank():
     """`bench.py --e2e` (tower -> projector -> prefill) on one rank with a two-layer prefill: the path must run and print its
     one line (a NameError lived here for half a round because nothing exercised it)."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--e2e", "--e2e-batch", "2", "--e2e-layers", "2", "--steps", "1", "--warmup", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--e2e", "--e2e-batch", "2", "--e2e-layers", "2", "--steps", "1", "--warmup", "1",
+           "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]

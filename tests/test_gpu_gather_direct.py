@@ -39,7 +39,7 @@ def test_direct_gather_between_processes(nproc, use_cus):
 def _bench_no_launcher(extra, n_lines=1, env_extra=None):
     """`python bench.py --gpus 2 ...` exactly as the driver types it for N > 1, with no torch.distributed.run around it."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--backend", "gloo",
-           "--single-device", "--no-cpu-baseline", "--batch", "8", "--min-seconds", "0.05"] + extra
+           "--single-device", "--no-cpu-baseline", "--batch", "8", "--min-seconds", "0.05", "--full"] + extra
     env = _env()
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)

@@ -64,7 +64,10 @@ def test_slice_oracle_matches_reference_dataloader_code():
         assert crops.shape[0] == hd.hd_crop_count(hb, wb)
         assert np.array_equal(crops[:, :, ::stride, ::stride].numpy(), z[f"sub_{k}"])
         s = z[f"sum_{k}"]
-        assert float(crops.double().sum()) == s[0] and float(crops.double().abs().sum()) == s[1]
+        # whole-crop float64 checksums: torch adds in an order set by its intra-op thread count, so the minted sums and these
+        # agree to float64 summation round-off (observed <= 2 ulp of the sum of |x|), not bit for bit
+        tol = 64 * np.finfo(np.float64).eps * s[1]
+        assert abs(float(crops.double().sum()) - s[0]) <= tol and abs(float(crops.double().abs().sum()) - s[1]) <= tol
         # the resized extent implied by the plan is where the canvas stops being zero-padded
         assert plan[2] <= 336 * hb and plan[3] <= 336 * wb and (plan[2] == 336 * hb or plan[3] == 336 * wb)
 
