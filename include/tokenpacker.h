@@ -33,7 +33,9 @@ extern "C" {
 /* ABI 5 (round 6): tp_linear_args.reserved1 became `ldw` and the packed-weight image's layout changed (w_cc_v3: interleaved
  * hi_t | lo_t K-tile pairs) — both already in round 5 under a stale 4 —, TP_TUNE_DECOUPLE_K and TP_TUNE_BWD_CHAIN (18 knobs), the probe instantiations
  * and test hooks left the product library (tokenpacker_test.h / libtokenpacker_exp.so), tp_debug_counter. */
-#define TP_ABI_VERSION 5
+/* ABI 6: additive — tp_input_grads, tp_backward_inputs_workspace_bytes, tp_backward_inputs and tp_backward_inputs_parts (opt-in
+ * gradients with respect to x / x_multi).  Every ABI 5 entry point, struct and workspace size is unchanged, and so are its results. */
+#define TP_ABI_VERSION 6
 
 typedef enum tp_status {
     TP_OK = 0,
@@ -306,7 +308,7 @@ int tp_linear_stats_parts(const tp_linear_args* args);
  * Stage-1 training of the reference updates ONLY the projector (llava/train/train.py:950-953); the CLIP features
  * come from a frozen, no_grad tower (clip_encoder.py:46).  tp_backward therefore produces the gradients of the
  * 23 parameters (tp_grads mirrors tp_weights, each tensor contiguous, element type desc.dtype) and none for
- * x / x_multi.  Replaces what autograd records for builder.py:107-137.
+ * x / x_multi; tp_backward_inputs (below) adds those on request.  Replaces what autograd records for builder.py:107-137.
  *   tp_forward_train : tp_forward + the fp16 pre-GELU activations, into a caller-owned `train_workspace`
  *                      (tp_train_workspace_bytes) that must stay untouched until tp_backward has run.
  *   tp_backward      : dy [B, M, D] contiguous (desc.dtype) -> grads; `raw` = the model's current parameters
@@ -338,6 +340,29 @@ int tp_forward_train_parts(const tp_desc* desc, const void* x, const int64_t x_s
 int tp_backward_parts(const tp_desc* desc, const void* const xm_parts[4], const int64_t part_strides[3],
                       const tp_weights* raw, const void* packed_weights, const void* train_workspace, const void* dy,
                       const tp_grads* grads, void* bw_workspace, size_t bw_workspace_bytes, void* stream);
+
+/* ABI 6: the backward with gradients with respect to the CLIP features (opt-in: a trainable or LoRA-tuned tower, attribution over
+ * the features).  Same arguments as tp_backward / tp_backward_parts plus `ig`, the input gradients wanted (each output contiguous,
+ * element type desc.dtype, 16-byte aligned; NULL = not wanted):
+ *   dx                 [B, N, 1024]: the transpose of the point queries' bilinear downsample applied to dQ1 · Wq1 (fp32, rounded once)
+ *   dx_multi           [B, N, 4096]: dZ1 · [Wk0; Wv0] (tp_backward_inputs only)
+ *   dx_multi_parts[4]  four [B, N, 1024]: the same product's column slices, bit for bit (tp_backward_inputs_parts only; all or none)
+ * `grads` may be NULL: no parameter gradient is computed (a frozen projector in front of a trainable tower).  The workspace is
+ * tp_backward_inputs_workspace_bytes (>= tp_backward_workspace_bytes; 0 on a bad descriptor), and its status word has the bits
+ * tp_backward's has.  Deterministic like tp_backward; the parameter gradients are those tp_backward computes, bit for bit. */
+typedef struct tp_input_grads {
+    void* dx;                  /* [B, N, 1024] contiguous, desc.dtype; NULL = not wanted                        */
+    void* dx_multi;            /* [B, N, 4096] contiguous; NULL = not wanted (concatenated form)                */
+    void* dx_multi_parts[4];   /* four [B, N, 1024] contiguous (the _parts entry point); NULL = none            */
+} tp_input_grads;
+size_t tp_backward_inputs_workspace_bytes(const tp_desc* desc);
+int tp_backward_inputs(const tp_desc* desc, const void* x_multi, const int64_t xm_strides[3], const tp_weights* raw,
+                       const void* packed_weights, const void* train_workspace, const void* dy, const tp_grads* grads,
+                       const tp_input_grads* ig, void* bw_workspace, size_t bw_workspace_bytes, void* stream);
+int tp_backward_inputs_parts(const tp_desc* desc, const void* const xm_parts[4], const int64_t part_strides[3],
+                             const tp_weights* raw, const void* packed_weights, const void* train_workspace, const void* dy,
+                             const tp_grads* grads, const tp_input_grads* ig, void* bw_workspace, size_t bw_workspace_bytes,
+                             void* stream);
 
 /* The backward's weight-gradient contraction on its own (what autograd computes for every nn.Linear of
  * builder.py:59-83):  dw[n_out, k_in] = sum over the `rows` token rows of dy[r, n] * x[r, k], read from the ROW-MAJOR

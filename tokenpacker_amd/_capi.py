@@ -11,7 +11,7 @@ import os
 from ctypes import (POINTER, Structure, byref, c_char_p, c_float, c_int, c_int32, c_int64,
                     c_size_t, c_uint32, c_uint64, c_void_p)
 
-TP_ABI_VERSION = 5
+TP_ABI_VERSION = 6
 TP_BF16, TP_F16, TP_F32 = 0, 1, 2
 TP_OK, TP_ERR_INVALID_ARG, TP_ERR_BAD_SCALE, TP_ERR_WORKSPACE, TP_ERR_LAUNCH = 0, -1, -2, -3, -4
 TP_LINEAR_GELU, TP_LINEAR_LN_FOLD, TP_LINEAR_ROW_STATS = 1, 2, 4
@@ -57,6 +57,7 @@ EXPORTED_SYMBOLS = (
     "tp_wgrad", "tp_wgrad_workspace_bytes", "tp_packed_status_offset", "tp_debug_count_saturated", "tp_debug_counter",
     "tp_region_attention_absorbed", "tp_forward_masked",
     "tp_get_tuning", "tp_release_stream",
+    "tp_backward_inputs_workspace_bytes", "tp_backward_inputs", "tp_backward_inputs_parts",
     "tp_tuning_create", "tp_tuning_destroy", "tp_tuning_set", "tp_tuning_get", "tp_gather_alloc_flags", "tp_gather_free_flags", "tp_gather_export", "tp_gather_open", "tp_gather_close", "tp_gather_push", "tp_gather_sync",
 )
 # include/tokenpacker_test.h: the stateless test hooks — libtokenpacker_exp.so only (load_test_library()), never the product library
@@ -93,6 +94,11 @@ class tp_weights(Structure):
 class tp_grads(Structure):
     """Output pointers of tp_backward: one gradient tensor per parameter, same order as tp_weights."""
     _fields_ = [(name.replace(".", "_"), c_void_p) for name in WEIGHT_FIELDS]
+
+
+class tp_input_grads(Structure):
+    """Output pointers of tp_backward_inputs*: the gradients with respect to x / x_multi that are wanted (NULL = not wanted)."""
+    _fields_ = [("dx", c_void_p), ("dx_multi", c_void_p), ("dx_multi_parts", c_void_p * 4)]
 
 
 class tp_linear_args(Structure):
@@ -215,6 +221,15 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.tp_backward_parts.restype = c_int
     lib.tp_backward_parts.argtypes = [POINTER(tp_desc), POINTER(c_void_p), POINTER(c_int64), POINTER(tp_weights), c_void_p,
                                       c_void_p, c_void_p, POINTER(tp_grads), c_void_p, c_size_t, c_void_p]
+    lib.tp_backward_inputs_workspace_bytes.restype = c_size_t
+    lib.tp_backward_inputs_workspace_bytes.argtypes = [POINTER(tp_desc)]
+    lib.tp_backward_inputs.restype = c_int
+    lib.tp_backward_inputs.argtypes = [POINTER(tp_desc), c_void_p, POINTER(c_int64), POINTER(tp_weights), c_void_p, c_void_p,
+                                       c_void_p, POINTER(tp_grads), POINTER(tp_input_grads), c_void_p, c_size_t, c_void_p]
+    lib.tp_backward_inputs_parts.restype = c_int
+    lib.tp_backward_inputs_parts.argtypes = [POINTER(tp_desc), POINTER(c_void_p), POINTER(c_int64), POINTER(tp_weights),
+                                             c_void_p, c_void_p, c_void_p, POINTER(tp_grads), POINTER(tp_input_grads), c_void_p,
+                                             c_size_t, c_void_p]
     lib.tp_wgrad_workspace_bytes.restype = c_size_t
     lib.tp_wgrad_workspace_bytes.argtypes = [c_int, c_int]
     lib.tp_wgrad.restype = c_int

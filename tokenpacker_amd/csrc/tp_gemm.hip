@@ -274,7 +274,7 @@ static int launch_types(const GemmArgs& a, hipStream_t stream) {
     const int tile = gemm_pick_tile(a.M, a.N, a.tile, a.groups);
     const bool strided = a.rows_per_batch < a.M || a.a_region_s > 0;     // (region-major rows: the strided-A kernels)
     constexpr bool HALF_OUT = !std::is_same<TO, float>::value;
-    const bool train_epi = (a.flags & (TP_LINEAR_SAVE_PRE | TP_LINEAR_GELU_BWD)) != 0;
+    const bool train_epi = (a.flags & (TP_LINEAR_SAVE_PRE | TP_LINEAR_GELU_BWD)) != 0 || a.out_scale;
     if ((a.flags & TP_LINEAR_NO_STORE) || a.acc_init) {     // the two GEMMs of the fused LayerNorm chain (128-tile form)
         if constexpr (std::is_same<TI, f16_t>::value && std::is_same<TO, f16_t>::value) {
             if (strided || train_epi || ((a.flags & TP_LINEAR_NO_STORE) && a.acc_init) || a.A_parts[0]) {
@@ -352,7 +352,7 @@ static int gemm_route(const GemmArgs& a, long long* head_rows_out) {
             // r04t_t192_ab.json).  A 32-image shard's first layer is 2.25 rounds of full tiles and exactly 3 of these, its mlp
             // launches 1.125 and 1.5.  Plain launches only (no training epilogue, no statistics: the kernel is built for XMODE 0).
             const bool plain = !(a.flags & (TP_LINEAR_SAVE_PRE | TP_LINEAR_GELU_BWD | TP_LINEAR_NO_STORE | TP_LINEAR_ROW_STATS)) &&
-                               !a.acc_init && !a.attn_mode && !a.stats_parts && !a.tri && a.tt_rows == 0;   // (K-major launches: never)
+                               !a.out_scale && !a.acc_init && !a.attn_mode && !a.stats_parts && !a.tri && a.tt_rows == 0;   // (K-major launches: never)
             const long long T192 = (long long)((a.M + 191) / 192) * tiles_n;
             const double cost_d = plain ? (a.K <= 1024 ? 0.87 : 0.85) * (double)rounds(T192) : 1e30;
             const double best_abc = cost_c < cost_a - 0.05 && cost_c <= cost_b && TH >= 64 ? cost_c : (cost_b < cost_a - 0.05 ? cost_b : cost_a);
@@ -363,7 +363,7 @@ static int gemm_route(const GemmArgs& a, long long* head_rows_out) {
     }
     // TP_TUNE_GEMM_TILE = 3 (tests, A/Bs): every tile of a plain launch a 192 x 256 tile
     if (tuning(TP_TUNE_GEMM_TILE) == 3 && a.tile == 0 && !a.half_tiles && !a.A_parts[0] && a.N % 256 == 0 && a.m_begin == 0 && a.m_end == 0 &&
-        !(a.flags & (TP_LINEAR_SAVE_PRE | TP_LINEAR_GELU_BWD | TP_LINEAR_NO_STORE | TP_LINEAR_ROW_STATS)) && !a.acc_init && !a.attn_mode &&
+        !(a.flags & (TP_LINEAR_SAVE_PRE | TP_LINEAR_GELU_BWD | TP_LINEAR_NO_STORE | TP_LINEAR_ROW_STATS)) && !a.out_scale && !a.acc_init && !a.attn_mode &&
         !a.stats_parts && !a.tri && a.tt_rows == 0)
         return ROUTE_G8_192;
     // TP_TUNE_GEMM_TILE = 2 (tests, A/Bs): every tile of the ping-pong kernel a 128 x 256 half tile

@@ -866,7 +866,7 @@ static int launch8_cfg(const GemmArgs& a, hipStream_t stream) {
 template <typename TI, typename TO>
 static int launch8_types(const GemmArgs& a, hipStream_t stream) {
     constexpr bool HALF_OUT = !std::is_same<TO, float>::value;
-    const bool train_epi = (a.flags & (TP_LINEAR_SAVE_PRE | TP_LINEAR_GELU_BWD)) != 0;
+    const bool train_epi = (a.flags & (TP_LINEAR_SAVE_PRE | TP_LINEAR_GELU_BWD)) != 0 || a.out_scale;
     if (a.tt_rows > 0) {                                // K-major operands (weight gradients): fp32 partials only
         if (a.tile192) { set_error("tp gemm8: 192-row tiles do not take K-major operands"); return TP_ERR_INVALID_ARG; }
         if constexpr (std::is_same<TO, float>::value)

@@ -269,6 +269,10 @@ __device__ __forceinline__ void gemm_epilogue(f32x4 (&acc)[WM / 16][WN / 16], co
 #endif
                 }
                 if constexpr (TRAIN_EPI) {
+                if (p.out_scale) {                         // (a scalar load: the value is the same for every lane and tile)
+                    const float sc = *(const __attribute__((address_space(4))) float*)p.out_scale;
+                    v0 *= sc; v1 *= sc;
+                }
                 if (flags & TP_LINEAR_GELU_BWD) {          // backward of a GELU layer: dZ = dA * gelu'(Z), Z fp16 [M, ldz]
                     const f16_t* zrow = (const f16_t*)(p.Z + g * p.z_gs) + (long long)(row_ok ? m : 0) * p.ldz + col_base;
                     const f16x4 z0 = *(const f16x4*)(zrow + j0 * 16), z1 = *(const f16x4*)(zrow + j1 * 16);

@@ -465,7 +465,7 @@ gemm_pair_kernel(const GemmArgs p, const int tiles_m, const int tiles_n, const i
 // Whether gemm_launch may send `a` to the pair kernel (shape / feature coverage; the routing POLICY is gemm_launch's).
 bool gemm_pair_supports(int in_dtype, int out_dtype, const GemmArgs& a) {
     if (a.tt_rows > 0 || a.half_tiles || a.m_begin != 0 || a.m_end != 0 || a.stats_parts || a.parts_k_groups) return false;
-    if (a.flags & (TP_LINEAR_SAVE_PRE | TP_LINEAR_GELU_BWD)) return false;
+    if ((a.flags & (TP_LINEAR_SAVE_PRE | TP_LINEAR_GELU_BWD)) || a.out_scale) return false;
     if (a.N % GP_BN != 0 || a.K % BK != 0 || a.K / BK < 3) return false;
     if (a.lda_bytes >= (1 << 23) || (a.ldw_bytes ? a.ldw_bytes : (long long)a.K * 2) >= (1 << 23)) return false;
     const bool f16io = in_dtype == TP_F16 && out_dtype == TP_F16;

@@ -150,6 +150,10 @@ struct GemmArgs {
     // (a device int32 the caller zeroed at some point), a wave that clamped anything ORs sat_bit into it.  One v_max3 per
     // two output elements and, for a tile that did saturate, one atomic — nothing otherwise.
     int* sat_flag; int sat_bit;
+    // Output scale (device, optional): the plain result is multiplied by out_scale[0] in fp32 before the conversion — the 1 / S of a
+    // backward chain that carries its gradients scaled by a power of two (exact).  A launch that sets it takes the training-epilogue
+    // instantiations (128-tile or ping-pong kernel; never the pair or the 192-row kernel).  NULL: no scaling.
+    const float* out_scale;
 };
 int gemm_launch(int in_dtype, int out_dtype, const GemmArgs& a, hipStream_t stream);
 int gemm_route_of(int in_dtype, int out_dtype, const GemmArgs& a);   // test hook: 0 small | 1 full | 2 half | 3 split | 4 192-row | 5 pair
@@ -202,6 +206,10 @@ inline int gemm_stats_parts(int N) { return N / 128; }   // one (sum, sumsq) sla
 // element type of the caller's tensors (x, weights), outputs are fp16.
 int point_queries_launch(int dtype, const void* x, const int64_t st[3], void* q0_f16, int B, int grid,
                          int s, hipStream_t stream);
+// dx [B, grid^2, 1024] (dtype, contiguous) = the transpose of the point queries' bilinear downsample applied to dq0 (fp32
+// [B*M, 1024]), times *inv_scale (device; NULL: 1)
+int point_queries_bwd_launch(int dtype, const float* dq0, const float* inv_scale, void* dx, int B, int grid, int s,
+                             hipStream_t stream);
 // mask (optional, fp32): additive attn_mask — mask_mode 1: [s*s], 2: [(M B) 8, s*s] (batch index = region * B + image)
 // region_major: K / V rows are in region-major order (GemmArgs::a_region_s) instead of the tower's raster order
 int region_attention_launch(const void* q, const void* k, const void* v, void* o, int B,

@@ -1,5 +1,6 @@
 // tp_kernels.hip — the HBM-bound pieces of the TokenPacker path for gfx950:
 //   * point_queries_kernel   : fp32 bilinear downsample -> coarse point queries  (builder.py:117-118)
+//   * point_queries_bwd_kernel: its transpose (the gradient with respect to x, opt-in input gradients)
 //   * region_attention_kernel: region gather + 8-head softmax(q·K^T/sqrt(d))·V with ONE query per
 //                              region (builder.py:96-105, 122-130)
 //   * pack_* kernels          : one-time weight preparation (LayerNorm fold, fp32 biases)
@@ -74,6 +75,55 @@ int point_queries_launch(int dtype, const void* x, const int64_t st[3], void* q0
         hipLaunchKernelGGL(point_queries_kernel<f16_t>, dim3(blocks), dim3(256), 0, stream,
                            (const f16_t*)x, (long long)st[0], (long long)st[1], (f16_t*)q0, B, grid, s, kEmbed);
     return check_launch("point_queries_kernel");
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Backward of the point queries: dx = (the transpose of the bilinear downsample above) · dq0.  The taps of coarse point
+// (i, j) lie inside its own s x s block and the blocks are disjoint, so every fine pixel receives from at most one query:
+// even s — rows / columns s*i+s/2-1 and s*i+s/2, weight 1/4 each; odd s — the centre pixel, weight 1 (s = 1: the identity);
+// every other pixel exactly 0.  No atomics, deterministic.  dq0 is fp32 [B*M, C] and may carry the backward chain's
+// power-of-two scale S (inv_scale = &(1 / S) on the device, NULL: 1); the fp32 product tap weight x dq0 x 1 / S is rounded
+// once to T.  One thread = 8 channels of one fine pixel; every pixel of the contiguous dx [B, g*g, C] is written.
+template <typename T>
+__global__ void __launch_bounds__(256)
+point_queries_bwd_kernel(const float* __restrict__ dq0, const float* __restrict__ inv_scale, T* __restrict__ dx,
+                         int B, int g, int s, int C) {
+    const int G = g / s, M = G * G, N = g * g, vecs = C / 8;
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long long)B * N * vecs) return;
+    const int cv = (int)(gid % vecs);
+    const long long pix = gid / vecs;
+    const int n = (int)(pix % N), b = (int)(pix / N);
+    const int r = n / g, c = n % g, i = r / s, j = c / s, a = r - i * s, e = c - j * s;
+    bool tap;
+    float w;
+    if (s & 1) { const int o = (s - 1) / 2; tap = a == o && e == o; w = 1.f; }
+    else { const int h = s / 2; tap = (a == h - 1 || a == h) && (e == h - 1 || e == h); w = 0.25f; }
+    float out[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) out[k] = 0.f;
+    if (tap) {
+        const float sc = inv_scale ? inv_scale[0] : 1.f;
+        const f32x4* src = (const f32x4*)(dq0 + ((long long)b * M + (long long)i * G + j) * C + cv * 8);
+        const f32x4 v0 = src[0], v1 = src[1];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { out[k] = w * v0[k] * sc; out[4 + k] = w * v1[k] * sc; }
+    }
+    store8(dx + pix * C + cv * 8, out);
+}
+
+int point_queries_bwd_launch(int dtype, const float* dq0, const float* inv_scale, void* dx, int B, int grid, int s,
+                             hipStream_t stream) {
+    const long long total = (long long)B * grid * grid * (kEmbed / 8);
+    if (total == 0) return TP_OK;
+    const unsigned blocks = (unsigned)((total + 255) / 256);
+    if (dtype == TP_BF16)
+        hipLaunchKernelGGL(point_queries_bwd_kernel<bf16_t>, dim3(blocks), dim3(256), 0, stream, dq0, inv_scale, (bf16_t*)dx,
+                           B, grid, s, kEmbed);
+    else
+        hipLaunchKernelGGL(point_queries_bwd_kernel<f16_t>, dim3(blocks), dim3(256), 0, stream, dq0, inv_scale, (f16_t*)dx,
+                           B, grid, s, kEmbed);
+    return check_launch("point_queries_bwd_kernel");
 }
 
 // ---------------------------------------------------------------------------------------------------

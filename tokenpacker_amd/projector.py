@@ -36,8 +36,10 @@ _DTYPES = {torch.bfloat16: _capi.TP_BF16, torch.float16: _capi.TP_F16}
 
 class _ProjectFn(torch.autograd.Function):
     """Autograd node of the HIP projector: ``tp_forward_train`` keeps the backward's operands in a per-call
-    workspace, ``tp_backward`` returns the gradients of the 23 parameters (the CLIP features come from a frozen
-    ``no_grad`` tower — reference clip_encoder.py:46, train.py:950-953 — and get none)."""
+    workspace, ``tp_backward`` returns the gradients of the 23 parameters.  The CLIP features come from a frozen
+    ``no_grad`` tower in the reference's recipe (clip_encoder.py:46, train.py:950-953) and get none — unless the module's
+    ``input_gradients`` switch let them in requiring grad: then ``tp_backward_inputs*`` also returns dx / dx_multi, computing
+    only what ``ctx.needs_input_grad`` asks for (no parameter gradients at all for a frozen projector)."""
 
     @staticmethod
     def forward(ctx, module, x, n_parts, *rest):
@@ -50,9 +52,18 @@ class _ProjectFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         train_ws, packed, *rest = ctx.saved_tensors
-        xm, params = rest[:ctx.n_parts], rest[ctx.n_parts:]
-        grads = ctx.module._launch_backward(ctx.desc, xm[0] if ctx.n_parts == 1 else xm, train_ws, packed, params, dy)
-        return (None, None, None) + (None,) * ctx.n_parts + tuple(grads)
+        n = ctx.n_parts
+        xm, params = rest[:n], rest[n:]
+        need = ctx.needs_input_grad                          # (module, x, n_parts, *x_multi, *params)
+        want_dx, want_dxm, want_params = need[1], any(need[3:3 + n]), any(need[3 + n:])
+        if not (want_dx or want_dxm):
+            grads = ctx.module._launch_backward(ctx.desc, xm[0] if n == 1 else xm, train_ws, packed, params, dy)
+            return (None, None, None) + (None,) * n + tuple(grads)
+        grads, dx, dxm = ctx.module._launch_backward(ctx.desc, xm[0] if n == 1 else xm, train_ws, packed, params, dy,
+                                                     want_params=want_params, want_dx=want_dx, want_dxm=want_dxm)
+        dxm = (dxm,) if n == 1 else (dxm or (None,) * n)
+        dxm = tuple(g if need[3 + i] else None for i, g in enumerate(dxm))
+        return (None, dx, None) + dxm + (tuple(grads) if grads is not None else (None,) * len(params))
 
 
 def _forget_packed(ptr: int) -> None:
@@ -106,6 +117,11 @@ class TokenPacker(nn.Module):
         #: set True to receive fp32 output straight from the last GEMM's accumulators
         #: (validation mode of SURVEY.md §8c; default = input dtype like the reference)
         self.output_fp32 = False
+        #: set True to differentiate with respect to the CLIP features too (a trainable or LoRA-tuned vision tower,
+        #: attribution over the features): x / x_multi that require grad then receive dx / dx_multi from the HIP backward
+        #: (tp_backward_inputs).  Default False, like the reference's recipe, whose tower is frozen and runs under no_grad
+        #: (clip_encoder.py:46): inputs that require grad are refused.  Training-only, like every autograd use of the module.
+        self.input_gradients = False
         #: fp32 callers.  The reference module runs in any dtype; the HIP kernels compute in bf16 / fp16 MFMA.  Under
         #: ``torch.autocast`` an fp32 module (fp32 master weights) is served in the autocast dtype like every
         #: ``nn.Linear`` of the reference would be.  Outside autocast an fp32 module is refused unless this names the
@@ -144,6 +160,7 @@ class TokenPacker(nn.Module):
         for k, v in self._CACHE_DEFAULTS.items():
             self.__dict__.setdefault(k, v)
         self.__dict__.setdefault("_workspaces", {})
+        self.__dict__.setdefault("input_gradients", False)        # (modules pickled before the switch existed)
 
     def _reset_parameters(self) -> None:
         """Same initial distribution as the reference (builder.py:87-94): truncated normal
@@ -332,10 +349,11 @@ class TokenPacker(nn.Module):
             raise ValueError(f"expected x [B,{N},{self.embed_dim}] and x_multi [B,{N},{self.MULTI_LEVEL_DIM}] "
                              f"(or four [B,{N},{self.MULTI_LEVEL_DIM // 4}] parts), "
                              f"got {tuple(x.shape)} and {[tuple(t.shape) for t in (parts or (x_multi,))]}")
-        if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in (parts or (x_multi,)))):
+        inputs_grad = torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in (parts or (x_multi,))))
+        if inputs_grad and not self.input_gradients:
             raise NotImplementedError(
-                "the HIP projector does not differentiate with respect to the CLIP features (the reference's tower is "
-                "frozen and runs under no_grad, clip_encoder.py:46); detach them")
+                "the HIP projector does not differentiate with respect to the CLIP features by default (the reference's tower "
+                "is frozen and runs under no_grad, clip_encoder.py:46); detach them, or set module.input_gradients = True")
         mask = self._attn_mask_operand(attn_mask, x.shape[0], x.device) if attn_mask is not None else None
         if mask is not None and (parts or _stage_events is not None):
             raise NotImplementedError("attn_mask takes the concatenated x_multi and no staged timing")
@@ -344,6 +362,8 @@ class TokenPacker(nn.Module):
             y = x.new_zeros((0, self.num_queries, self.hidden_size), dtype=out_dtype) if _out is None else _out
             if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
                 y = y + 0.0 * sum(p.sum() for p in self.parameters() if p.requires_grad).to(out_dtype)
+            if inputs_grad:                  # (connected too: their gradients come back as zeros)
+                y = y + 0.0 * sum(t.sum() for t in (x, *(parts or (x_multi,))) if t.requires_grad).to(out_dtype)
             return y
         if x.dtype != compute_dtype:                  # autocast / fp32 caller: operands rounded once, like autocast's casts
             x = x.to(compute_dtype)
@@ -360,7 +380,7 @@ class TokenPacker(nn.Module):
             x_multi = parts
         else:
             x_multi = self._addressable(x_multi)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        if inputs_grad or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
             if _stage_events is not None or self.output_fp32 or fp32_caller or _out is not None or mask is not None:
                 raise NotImplementedError("staged timing / fp32 output / fp32_compute_dtype / _out / attn_mask are inference-only")
             # (partially frozen projectors — e.g. LoRA-style experiments freezing the K/V branches — go through the same
@@ -518,7 +538,11 @@ class TokenPacker(nn.Module):
                         "tp_debug_count_saturated")
             return dict(zip(_capi.DEBUG_BUFFER_NAMES, counts.tolist()))
 
-    def _launch_backward(self, desc, x_multi, train_ws, packed, params, dy):
+    def _launch_backward(self, desc, x_multi, train_ws, packed, params, dy, want_params=True, want_dx=False, want_dxm=False):
+        """-> the 23 parameter gradients (tp_backward*); with ``want_dx`` / ``want_dxm`` (tp_backward_inputs*) ->
+        ``(parameter gradients or None, dx or None, dx_multi or None)`` — dx_multi one [B, N, 4096] tensor, or a tuple of the
+        four sources' [B, N, 1024] gradients when x_multi came as parts."""
+        inputs = want_dx or want_dxm
         parts = tuple(x_multi) if isinstance(x_multi, (tuple, list)) else None
         if parts:
             x_multi = parts[0]
@@ -530,13 +554,43 @@ class TokenPacker(nn.Module):
             # compute dtype for the dgrad operands exactly as they were for the forward
             contiguous = [p.detach().to(x_multi.dtype).contiguous() for p in params]
             raw = _capi.tp_weights(*[t.data_ptr() for t in contiguous])
-            grads = [torch.empty_like(t) for t in contiguous]
-            gptr = _capi.tp_grads(*[t.data_ptr() for t in grads])
-            bw_bytes = lib.tp_backward_workspace_bytes(ctypes.byref(desc))
+            grads = [torch.empty_like(t) for t in contiguous] if want_params else None
+            gptr = _capi.tp_grads(*[t.data_ptr() for t in grads]) if want_params else None
+            bw_bytes = (lib.tp_backward_inputs_workspace_bytes if inputs else lib.tp_backward_workspace_bytes)(ctypes.byref(desc))
             if bw_bytes == 0:
                 raise RuntimeError(f"tp_backward_workspace_bytes: {_capi.last_error()}")
             bw = self._workspace(bw_bytes, device, ("bwd", stream_ptr))
             dy = dy.to(x_multi.dtype).contiguous()
+            if inputs:
+                B, N, E = desc.batch, self.raw_grid * self.raw_grid, self.embed_dim
+                new = partial(torch.empty, dtype=x_multi.dtype, device=device)
+                dx = new(B, N, E) if want_dx else None
+                ig = _capi.tp_input_grads()
+                ig.dx = dx.data_ptr() if want_dx else None
+                dxm = None
+                if want_dxm and parts:
+                    dxm = tuple(new(B, N, self.MULTI_LEVEL_DIM // 4) for _ in range(4))
+                    for i, t in enumerate(dxm):
+                        ig.dx_multi_parts[i] = t.data_ptr()
+                elif want_dxm:
+                    dxm = new(B, N, self.MULTI_LEVEL_DIM)
+                    ig.dx_multi = dxm.data_ptr()
+                g_arg = ctypes.byref(gptr) if want_params else None
+                if parts:
+                    part_ptrs = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in parts])
+                    _capi.check(lib.tp_backward_inputs_parts(ctypes.byref(desc), part_ptrs, _capi.strides3(parts[0].stride()),
+                                                             ctypes.byref(raw), packed.data_ptr(), train_ws.data_ptr(),
+                                                             dy.data_ptr(), g_arg, ctypes.byref(ig), bw.data_ptr(), bw.numel(),
+                                                             stream_ptr), "tp_backward_inputs_parts")
+                else:
+                    _capi.check(lib.tp_backward_inputs(ctypes.byref(desc), x_multi.data_ptr(), _capi.strides3(x_multi.stride()),
+                                                       ctypes.byref(raw), packed.data_ptr(), train_ws.data_ptr(), dy.data_ptr(),
+                                                       g_arg, ctypes.byref(ig), bw.data_ptr(), bw.numel(), stream_ptr),
+                                "tp_backward_inputs")
+                self._watch_backward_status(bw, device)
+                if grads is not None:
+                    grads = [g if g.dtype == p.dtype else g.to(p.dtype) for g, p in zip(grads, params)]
+                return grads, dx, dxm
             if parts:
                 part_ptrs = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in parts])
                 _capi.check(lib.tp_backward_parts(ctypes.byref(desc), part_ptrs, _capi.strides3(parts[0].stride()),

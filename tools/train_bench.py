@@ -8,6 +8,9 @@ the backward re-transpose the weights, so it belongs inside the timed step.  FLO
 backward actually has to do: no input gradient for k/v_proj_1[0] (the CLIP features come from a frozen tower).
 
     python tools/train_bench.py [--batches 32 256] [--scale-factor 2] [--out gpurun_out/train_bench.json]
+
+--input-grads also times the step with the opt-in gradients with respect to x and x_multi (module.input_gradients, both
+inputs requiring grad) and prices the two extra dgrads: dx_multi = dZ1 · [Wk0; Wv0] and dq0 = dQ1pre · Wq1.
 """
 import argparse
 import json
@@ -35,6 +38,12 @@ def flops_train(B, s, D):
     return 3.0 * flops_fwd(B, s, D) - 2.0 * B * (N * 4096 * E * 2)
 
 
+def flops_input_grads(B, s):
+    """the two dgrads the input gradients add: dx_multi [B*N, 4096] over K = 2048 and dq0 [B*M, 1024] over K = 1024"""
+    N, M, E = 576, (24 // s) ** 2, 1024
+    return 2.0 * B * (N * 2 * E * 4096 + M * E * E)
+
+
 def timed(fn, iters, warm=3):
     for _ in range(warm):
         fn()
@@ -54,6 +63,7 @@ def main():
     ap.add_argument("--out", default="gpurun_out/train_bench.json")
     ap.add_argument("--hip-only", action="store_true", help="skip the eager baseline (profiling runs)")
     ap.add_argument("--optimizer", default="sgd", choices=["sgd", "none"])
+    ap.add_argument("--input-grads", action="store_true", help="also time the step with gradients with respect to x / x_multi")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE", help="library tuning knob, e.g. BWD_CHAIN=1")
     args = ap.parse_args()
     from tokenpacker_amd import _capi
@@ -91,15 +101,37 @@ def main():
             with torch.no_grad():
                 m((x, xm))
 
+        x_in, xm_in = x.clone().requires_grad_(True), xm.clone().requires_grad_(True)
+
+        def step_hip_inputs():
+            m.zero_grad(set_to_none=True)
+            x_in.grad = xm_in.grad = None
+            m.input_gradients = True
+            (m((x_in, xm_in)) * w).sum().backward()
+            m.input_gradients = False
+            if opt is not None:
+                opt.step()
+
         iters = 20 if B <= 64 else 8
         ms_hip = timed(step_hip, iters)
+        ig = {}
+        if args.input_grads:
+            ms_in = timed(step_hip_inputs, iters)
+            ig = {"hip_fwd_bwd_input_grads_ms": round(ms_in, 3), "input_grads_extra_ms": round(ms_in - ms_hip, 3),
+                  "input_grads_extra_gflop": round(flops_input_grads(B, s) / 1e9, 1),
+                  "input_grads_extra_tflops": round(flops_input_grads(B, s) / max(ms_in - ms_hip, 1e-6) / 1e9, 1)}
+            x_in.grad = xm_in.grad = None
         ms_eager = timed(step_eager, iters) if not args.hip_only else float("nan")
         ms_fwd = timed(fwd_hip, iters)
         # gradient agreement of the two bf16 pipelines (sanity, loose)
         # (ln_k_1.bias and the k third of in_proj_bias have a mathematically zero gradient: round-off in both)
         E = 1024
         if args.hip_only:
-            print(json.dumps({"B": B, "hip_fwd_bwd_ms": round(ms_hip, 3), "hip_fwd_only_ms": round(ms_fwd, 3)}), flush=True)
+            rec = {"B": B, "hip_fwd_bwd_ms": round(ms_hip, 3), "hip_fwd_only_ms": round(ms_fwd, 3), **ig}
+            print(json.dumps(rec), flush=True)
+            results.append(rec)
+            del m, x, xm, w, x_in, xm_in
+            torch.cuda.empty_cache()
             continue
         finite = {"hip": all(bool(torch.isfinite(p.float()).all()) for p in m.parameters()),
                   "eager": all(bool(torch.isfinite(p.float()).all()) for p in m_eager.parameters())}
@@ -118,10 +150,10 @@ def main():
                "optimizer_in_step": args.optimizer,
                "train_tflops_algorithmic": round(flops_train(B, s, D) / ms_hip / 1e9, 1),
                "train_gflop_per_image": round(flops_train(1, s, D) / 1e9, 2),
-               "weights_finite_after_training": finite, "max_param_grad_rel_l2_vs_eager": agree, "tune": args.tune}
+               "weights_finite_after_training": finite, "max_param_grad_rel_l2_vs_eager": agree, "tune": args.tune, **ig}
         print(json.dumps(rec), flush=True)
         results.append(rec)
-        del m, m_eager, x, xm, w
+        del m, m_eager, x, xm, w, x_in, xm_in
         torch.cuda.empty_cache()
     os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
     json.dump(results, open(args.out, "w"), indent=1)
