@@ -35,6 +35,8 @@ extern "C" {
  * and test hooks left the product library (tokenpacker_test.h / libtokenpacker_exp.so), tp_debug_counter. */
 /* ABI 6: additive — tp_input_grads, tp_backward_inputs_workspace_bytes, tp_backward_inputs and tp_backward_inputs_parts (opt-in
  * gradients with respect to x / x_multi).  Every ABI 5 entry point, struct and workspace size is unchanged, and so are its results. */
+/* ABI 6, extended (detected by symbol; the version stays 6): tp_attn_mask, tp_forward_train_masked, tp_forward_parts_masked and
+ * tp_backward_masked (training with an attn_mask, and its gradient).  Nothing else changes. */
 #define TP_ABI_VERSION 6
 
 typedef enum tp_status {
@@ -177,7 +179,8 @@ int tp_forward(const tp_desc* desc,
  * 0 / -inf).  mask_mode 1: attn_mask [s*s] — the reference's 2-D (L=1, S=s*s) form, shared by every image, region
  * and head; mask_mode 2: attn_mask [(M*B)*8, s*s] — its 3-D (N*num_heads, L=1, S) form with the reference's batch
  * index N = region * B + image (divide_feature's order, builder.py:96-105); mask_mode 0: none.  Key index inside a
- * region: a*s + b for fine token (i*s + a, j*s + b).  Inference only. */
+ * region: a*s + b for fine token (i*s + a, j*s + b).  Inference; training with a mask: tp_forward_train_masked /
+ * tp_backward_masked (below). */
 int tp_forward_masked(const tp_desc* desc,
                       const void* x, const int64_t x_strides[3],
                       const void* x_multi, const int64_t xm_strides[3],
@@ -363,6 +366,43 @@ int tp_backward_inputs_parts(const tp_desc* desc, const void* const xm_parts[4],
                              const tp_weights* raw, const void* packed_weights, const void* train_workspace, const void* dy,
                              const tp_grads* grads, const tp_input_grads* ig, void* bw_workspace, size_t bw_workspace_bytes,
                              void* stream);
+
+/* ABI 6 extension (a binding detects it by symbol): training with the `attn_mask` of tp_forward_masked.  The masked training
+ * forward runs the training schedule (which writes K | V anyway: its workspace is tp_train_workspace_bytes, mask or not) with the
+ * mask in the attention logits; the masked backward adds the mask to the logits it recomputes, and — when `grad` is non-NULL —
+ * returns dL/dmask, the gradient of an additive float mask that is a learnable region bias in the reference (an ordinary
+ * autograd leaf there).
+ *   mask   fp32 additive mask, laid out as tp_forward_masked takes it (mode 1: [s*s]; mode 2: [(M*B)*8, s*s], batch index
+ *          region * B + image) — the SAME values the training forward of this step was given
+ *   mode   1 or 2 (0 with mask == NULL and grad == NULL: no mask — the call is then tp_backward_inputs' / tp_backward's)
+ *   grad   NULL, or fp32 in the mask's layout: dL/dmask_j = p_j (dP_j - D) summed over whatever shares entry j (mode 1: every
+ *          image, query and head; mode 2: nothing — each entry is written once).  Unscaled: the fp16 gradient chain's dynamic
+ *          scale is taken out on the device.  Deterministic (mode 1 sums per-query partials in a fixed order), no atomics.
+ * A fully masked row (every key of some head at -inf) gives a non-finite output, as in the reference, and non-finite
+ * gradients.  A per-head mask (mode 2) needs the whole batch in one launch, as in inference.
+ *   tp_forward_train_masked  xm_parts NULL: x_multi concatenated (xm_strides its strides); non-NULL: the four sources of
+ *                            tp_forward_train_parts (xm_strides their common strides; x_multi ignored)
+ *   tp_forward_parts_masked  inference: tp_forward_parts with a mask (workspace sized with TP_DESC_MASKED)
+ *   tp_backward_masked       tp_backward_inputs(_parts) with the mask: `grads` and `ig` are both nullable (at least one of them
+ *                            or mask->grad must be asked for); `ig` non-NULL takes tp_backward_inputs_workspace_bytes, NULL
+ *                            tp_backward_workspace_bytes — no further scratch.  xm_parts as for tp_forward_train_masked.
+ * Without a mask (mode 0) every result is tp_backward's / tp_backward_inputs', bit for bit. */
+typedef struct tp_attn_mask {
+    const float* mask;         /* fp32 additive mask (tp_forward_masked's layout); NULL iff mode == 0            */
+    int32_t mode;              /* 1: [s*s] shared by everything; 2: [(M*B)*8, s*s]; 0: none                       */
+    int32_t reserved;          /* must be 0 (anything else: TP_ERR_INVALID_ARG)                                   */
+    float* grad;               /* NULL, or dL/dmask in the mask's layout (fp32)                                  */
+} tp_attn_mask;
+int tp_forward_train_masked(const tp_desc* desc, const void* x, const int64_t x_strides[3], const void* x_multi,
+                            const void* const xm_parts[4], const int64_t xm_strides[3], const void* packed_weights, void* out,
+                            void* train_workspace, size_t workspace_bytes, const float* attn_mask, int mask_mode, void* stream);
+int tp_forward_parts_masked(const tp_desc* desc, const void* x, const int64_t x_strides[3], const void* const xm_parts[4],
+                            const int64_t part_strides[3], const void* packed_weights, void* out, void* workspace,
+                            size_t workspace_bytes, const float* attn_mask, int mask_mode, void* stream);
+int tp_backward_masked(const tp_desc* desc, const void* x_multi, const void* const xm_parts[4], const int64_t xm_strides[3],
+                       const tp_weights* raw, const void* packed_weights, const void* train_workspace, const void* dy,
+                       const tp_grads* grads, const tp_input_grads* ig, const tp_attn_mask* mask, void* bw_workspace,
+                       size_t bw_workspace_bytes, void* stream);
 
 /* The backward's weight-gradient contraction on its own (what autograd computes for every nn.Linear of
  * builder.py:59-83):  dw[n_out, k_in] = sum over the `rows` token rows of dy[r, n] * x[r, k], read from the ROW-MAJOR

@@ -58,6 +58,7 @@ EXPORTED_SYMBOLS = (
     "tp_region_attention_absorbed", "tp_forward_masked",
     "tp_get_tuning", "tp_release_stream",
     "tp_backward_inputs_workspace_bytes", "tp_backward_inputs", "tp_backward_inputs_parts",
+    "tp_forward_train_masked", "tp_forward_parts_masked", "tp_backward_masked",
     "tp_tuning_create", "tp_tuning_destroy", "tp_tuning_set", "tp_tuning_get", "tp_gather_alloc_flags", "tp_gather_free_flags", "tp_gather_export", "tp_gather_open", "tp_gather_close", "tp_gather_push", "tp_gather_sync",
 )
 # include/tokenpacker_test.h: the stateless test hooks — libtokenpacker_exp.so only (load_test_library()), never the product library
@@ -99,6 +100,12 @@ class tp_grads(Structure):
 class tp_input_grads(Structure):
     """Output pointers of tp_backward_inputs*: the gradients with respect to x / x_multi that are wanted (NULL = not wanted)."""
     _fields_ = [("dx", c_void_p), ("dx_multi", c_void_p), ("dx_multi_parts", c_void_p * 4)]
+
+
+class tp_attn_mask(Structure):
+    """The attn_mask of tp_forward_train_masked's step for tp_backward_masked: the fp32 additive mask, its mode (1: [s*s], 2:
+    [(M*B)*8, s*s]) and where dL/dmask goes (NULL = not wanted)."""
+    _fields_ = [("mask", c_void_p), ("mode", c_int32), ("reserved", c_int32), ("grad", c_void_p)]
 
 
 class tp_linear_args(Structure):
@@ -230,6 +237,15 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.tp_backward_inputs_parts.argtypes = [POINTER(tp_desc), POINTER(c_void_p), POINTER(c_int64), POINTER(tp_weights),
                                              c_void_p, c_void_p, c_void_p, POINTER(tp_grads), POINTER(tp_input_grads), c_void_p,
                                              c_size_t, c_void_p]
+    lib.tp_forward_train_masked.restype = c_int
+    lib.tp_forward_train_masked.argtypes = [POINTER(tp_desc), c_void_p, POINTER(c_int64), c_void_p, POINTER(c_void_p),
+                                            POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p]
+    lib.tp_forward_parts_masked.restype = c_int
+    lib.tp_forward_parts_masked.argtypes = lib.tp_forward_parts.argtypes[:-1] + [c_void_p, c_int, c_void_p]
+    lib.tp_backward_masked.restype = c_int
+    lib.tp_backward_masked.argtypes = [POINTER(tp_desc), c_void_p, POINTER(c_void_p), POINTER(c_int64), POINTER(tp_weights),
+                                       c_void_p, c_void_p, c_void_p, POINTER(tp_grads), POINTER(tp_input_grads),
+                                       POINTER(tp_attn_mask), c_void_p, c_size_t, c_void_p]
     lib.tp_wgrad_workspace_bytes.restype = c_size_t
     lib.tp_wgrad_workspace_bytes.argtypes = [c_int, c_int]
     lib.tp_wgrad.restype = c_int

@@ -1170,6 +1170,15 @@ int tp_forward_parts(const tp_desc* desc, const void* x, const int64_t x_strides
                         stream, nullptr, false, xm_parts);
 }
 
+int tp_forward_parts_masked(const tp_desc* desc, const void* x, const int64_t x_strides[3], const void* const xm_parts[4],
+                            const int64_t part_strides[3], const void* packed_weights, void* out, void* workspace,
+                            size_t workspace_bytes, const float* attn_mask, int mask_mode, void* stream) {
+    if (!xm_parts) { set_error("tp_forward_parts_masked: xm_parts is NULL"); return TP_ERR_INVALID_ARG; }
+    if ((mask_mode != 0 && !attn_mask) || mask_mode < 0 || mask_mode > 2) { set_error("tp_forward_parts_masked: bad mask / mask_mode"); return TP_ERR_INVALID_ARG; }
+    return forward_impl(desc, x, x_strides, nullptr, part_strides, packed_weights, out, workspace, workspace_bytes,
+                        stream, nullptr, false, xm_parts, mask_mode ? attn_mask : nullptr, mask_mode);
+}
+
 int tp_forward_staged(const tp_desc* desc, const void* x, const int64_t x_strides[3], const void* x_multi,
                       const int64_t xm_strides[3], const void* packed_weights, void* out, void* workspace,
                       size_t workspace_bytes, void* stream, void* const* stage_events, int n_events) {

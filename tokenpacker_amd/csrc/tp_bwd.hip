@@ -228,7 +228,7 @@ reduce_cols_stage1_kernel(const float* __restrict__ part, long long part_stride,
 }
 
 int bw_reduce_many_parts_launch(int dst_dtype, const float* part, long long part_stride, int nparts, int n, void* out,
-                                float* scratch, hipStream_t stream, const float* out_scale) {
+                                float* scratch, hipStream_t stream, const float* out_scale, int n_out) {
     if ((n & 3) || (part_stride & 3) || ((uintptr_t)part & 15)) {
         set_error("bw reduce: n / part stride must be multiples of 4 floats, partials 16-byte aligned");
         return TP_ERR_INVALID_ARG;
@@ -238,7 +238,7 @@ int bw_reduce_many_parts_launch(int dst_dtype, const float* part, long long part
     hipLaunchKernelGGL(reduce_cols_stage1_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)S), dim3(256), 0, stream,
                        part, part_stride, nparts, n, scratch);
     if (int rc = check_launch("reduce_cols_stage1_kernel")) return rc;
-    return bw_reduce_parts_launch(dst_dtype, scratch, n, S, n, out, stream, out_scale);
+    return bw_reduce_parts_launch(dst_dtype, scratch, n, S, n_out < 0 ? n : n_out, out, stream, out_scale);
 }
 
 // Column sums of a row-major 16-bit matrix (bias gradients of the layers whose weight gradient reads dY in place):
@@ -499,11 +499,18 @@ int bw_ln_backward_launch(int gdtype, const void* dy, const void* x_f16, const f
 // Every key/value row belongs to exactly one query (regions partition the grid), so dK / dV rows are written
 // once, without atomics.  Three sweeps over the region's keys (max+denominator | D and dV | dq and dK) keep the
 // kernel valid for any s; K/V are fp16 forward activations, dO / dQ / dK / dV the gradient dtype TG.
-template <typename TG>
+// MASKED: the additive attn_mask enters the recomputed logits of all three sweeps, indexed as
+// the forward kernel indexes it (mode 1: mask[kk]; mode 2: mask[((m B + b) 8 + h) s² + kk]); dQ / dK / dV keep their formulas.
+// dL/dmask_j = p_j (dP_j - D) (dS_j without the 1/sqrt(128)), times the fp16 chain's 1 / S (`inv_scale`, on the device; NULL:
+// unscaled), fp32 — mode 2: written once per (region·B + image, head, key) into `dmask`; mode 1: the wave's sum over its 8 heads
+// (fixed butterfly order) into `dmask_part[qi][S2p]`, reduced in a fixed order by bw_region_attention_masked_launch.
+template <typename TG, bool MASKED>
 __global__ void __launch_bounds__(256)
 region_attention_bwd_kernel(const f16_t* __restrict__ q, const f16_t* __restrict__ k, const f16_t* __restrict__ v,
                             const TG* __restrict__ dout, TG* __restrict__ dq, TG* __restrict__ dk, TG* __restrict__ dv,
-                            int B, int g, int s, float scale, int* __restrict__ sat_flag) {
+                            int B, int g, int s, float scale, int* __restrict__ sat_flag, const float* __restrict__ mask,
+                            int mask_mode, float* __restrict__ dmask, float* __restrict__ dmask_part, int S2p,
+                            const float* __restrict__ inv_scale) {
     float sat_mx = 0.f;
     auto trk = [&](float v) __attribute__((always_inline)) { const float a = fabsf(v); sat_mx = (a != a || a > sat_mx) ? a : sat_mx; return v; };
     constexpr int E = kEmbed;
@@ -518,6 +525,30 @@ region_attention_bwd_kernel(const f16_t* __restrict__ q, const f16_t* __restrict
     auto row_of = [&](int kk) -> long long {
         const int a = kk / s, c = kk - a * s;
         return ((long long)b * N + (i * s + a) * g + j * s + c) * E;
+    };
+    const float* mrow_a = nullptr; const float* mrow_b = nullptr;      // (MASKED: this lane's two heads' mask rows)
+    long long mo_a = 0, mo_b = 0;                                      // (mode 2: offsets of those rows, also dmask's)
+    if constexpr (MASKED) {
+        if (mask_mode == 2) {
+            const long long bi = (long long)m * B + b;
+            mo_a = (bi * kHeads + (lane >> 4)) * S2;
+            mo_b = (bi * kHeads + 4 + (lane >> 4)) * S2;
+        }
+        mrow_a = mask + mo_a; mrow_b = mask + mo_b;
+    }
+    // logits (for the max) and the exponent's argument logit - max: the unmasked kernel's d * scale - max contracts to ONE fma,
+    // the masked one is fma(d, scale, mask - max) — an all-zero mask gives the unmasked kernel's bits
+    auto logit_a = [&](float d, int kk) __attribute__((always_inline)) {
+        if constexpr (MASKED) return fmaf(d, scale, mrow_a[kk]); else return d * scale;
+    };
+    auto logit_b = [&](float d, int kk) __attribute__((always_inline)) {
+        if constexpr (MASKED) return fmaf(d, scale, mrow_b[kk]); else return d * scale;
+    };
+    auto arg_a = [&](float d, int kk, float mx) __attribute__((always_inline)) {
+        if constexpr (MASKED) return fmaf(d, scale, mrow_a[kk] - mx); else return d * scale - mx;
+    };
+    auto arg_b = [&](float d, int kk, float mx) __attribute__((always_inline)) {
+        if constexpr (MASKED) return fmaf(d, scale, mrow_b[kk] - mx); else return d * scale - mx;
     };
     auto load8h = [&](const f16_t* p, float (&f)[8]) {
         const f16x8 t = *(const f16x8*)p;
@@ -546,7 +577,7 @@ region_attention_bwd_kernel(const f16_t* __restrict__ q, const f16_t* __restrict
         float da = 0.f, db = 0.f;
 #pragma unroll
         for (int e = 0; e < 8; ++e) { da = fmaf(qa[e], ka[e], da); db = fmaf(qb[e], kb[e], db); }
-        mxa = fmaxf(mxa, dot16(da) * scale); mxb = fmaxf(mxb, dot16(db) * scale);
+        mxa = fmaxf(mxa, logit_a(dot16(da), kk)); mxb = fmaxf(mxb, logit_b(dot16(db), kk));
     }
     float dena = 0.f, denb = 0.f;
     for (int kk = 0; kk < S2; ++kk) {
@@ -556,7 +587,7 @@ region_attention_bwd_kernel(const f16_t* __restrict__ q, const f16_t* __restrict
         float da = 0.f, db = 0.f;
 #pragma unroll
         for (int e = 0; e < 8; ++e) { da = fmaf(qa[e], ka[e], da); db = fmaf(qb[e], kb[e], db); }
-        dena += __expf(dot16(da) * scale - mxa); denb += __expf(dot16(db) * scale - mxb);
+        dena += __expf(arg_a(dot16(da), kk, mxa)); denb += __expf(arg_b(dot16(db), kk, mxb));
     }
     const float inva = 1.0f / dena, invb = 1.0f / denb;
     // sweep 2: D = sum_j p_j dP_j, and dV
@@ -572,7 +603,7 @@ region_attention_bwd_kernel(const f16_t* __restrict__ q, const f16_t* __restrict
             da = fmaf(qa[e], ka[e], da); db = fmaf(qb[e], kb[e], db);
             pa_ = fmaf(doa[e], va[e], pa_); pb_ = fmaf(dob[e], vb[e], pb_);
         }
-        const float pa = __expf(dot16(da) * scale - mxa) * inva, pb = __expf(dot16(db) * scale - mxb) * invb;
+        const float pa = __expf(arg_a(dot16(da), kk, mxa)) * inva, pb = __expf(arg_b(dot16(db), kk, mxb)) * invb;
         Da = fmaf(pa, dot16(pa_), Da); Db = fmaf(pb, dot16(pb_), Db);
         G8 oa, ob;
 #pragma unroll
@@ -594,8 +625,22 @@ region_attention_bwd_kernel(const f16_t* __restrict__ q, const f16_t* __restrict
             da = fmaf(qa[e], ka[e], da); db = fmaf(qb[e], kb[e], db);
             pa_ = fmaf(doa[e], va[e], pa_); pb_ = fmaf(dob[e], vb[e], pb_);
         }
-        const float pa = __expf(dot16(da) * scale - mxa) * inva, pb = __expf(dot16(db) * scale - mxb) * invb;
+        const float pa = __expf(arg_a(dot16(da), kk, mxa)) * inva, pb = __expf(arg_b(dot16(db), kk, mxb)) * invb;
         const float dsa = pa * (dot16(pa_) - Da) * scale, dsb = pb * (dot16(pb_) - Db) * scale;
+        if constexpr (MASKED) {
+            if (dmask || dmask_part) {
+                const float isc = inv_scale ? inv_scale[0] : 1.0f;
+                const float gma = pa * (dot16(pa_) - Da) * isc, gmb = pb * (dot16(pb_) - Db) * isc;
+                if (mask_mode == 2) {
+                    if ((lane & 15) == 0) { dmask[mo_a + kk] = gma; dmask[mo_b + kk] = gmb; }
+                } else {
+                    float t = gma + gmb;                 // heads lane>>4 and 4 + (lane>>4), then the four head groups
+                    t += __shfl_xor(t, 16);
+                    t += __shfl_xor(t, 32);
+                    if (lane == 0) dmask_part[qi * S2p + kk] = t;
+                }
+            }
+        }
         G8 oa, ob;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -608,6 +653,9 @@ region_attention_bwd_kernel(const f16_t* __restrict__ q, const f16_t* __restrict
 #pragma unroll
     for (int e = 0; e < 8; ++e) { oa[e] = sat_cast<TG>(trk(dqa[e])); ob[e] = sat_cast<TG>(trk(dqb[e])); }
     *(G8*)(dq + qi * E + ea) = oa; *(G8*)(dq + qi * E + eb) = ob;
+    if constexpr (MASKED) {
+        if (dmask_part && mask_mode == 1 && lane < S2p - S2) dmask_part[qi * S2p + S2 + lane] = 0.f;   // (the row's padding)
+    }
     bw_sat_report<TG>(sat_flag, 4, sat_mx);
 }
 
@@ -618,12 +666,42 @@ int bw_region_attention_launch(int gdtype, const void* q, const void* k, const v
     const unsigned blocks = (unsigned)((nq + 3) / 4);
     const float scale = 0.08838834764831845f;   // 1/sqrt(128)
     if (gdtype == TP_BF16)
-        hipLaunchKernelGGL(region_attention_bwd_kernel<bf16_t>, dim3(blocks), dim3(256), 0, stream, (const f16_t*)q,
-                           (const f16_t*)k, (const f16_t*)v, (const bf16_t*)dout, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, B, grid, s, scale, sat_flag);
+        hipLaunchKernelGGL((region_attention_bwd_kernel<bf16_t, false>), dim3(blocks), dim3(256), 0, stream, (const f16_t*)q,
+                           (const f16_t*)k, (const f16_t*)v, (const bf16_t*)dout, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, B, grid, s, scale, sat_flag,
+                           nullptr, 0, nullptr, nullptr, 0, nullptr);
     else
-        hipLaunchKernelGGL(region_attention_bwd_kernel<f16_t>, dim3(blocks), dim3(256), 0, stream, (const f16_t*)q,
-                           (const f16_t*)k, (const f16_t*)v, (const f16_t*)dout, (f16_t*)dq, (f16_t*)dk, (f16_t*)dv, B, grid, s, scale, sat_flag);
+        hipLaunchKernelGGL((region_attention_bwd_kernel<f16_t, false>), dim3(blocks), dim3(256), 0, stream, (const f16_t*)q,
+                           (const f16_t*)k, (const f16_t*)v, (const f16_t*)dout, (f16_t*)dq, (f16_t*)dk, (f16_t*)dv, B, grid, s, scale, sat_flag,
+                           nullptr, 0, nullptr, nullptr, 0, nullptr);
     return check_launch("region_attention_bwd_kernel");
+}
+
+int bw_region_attention_masked_launch(int gdtype, const void* q, const void* k, const void* v, const void* dout, void* dq,
+                                      void* dk, void* dv, int B, int grid, int s, hipStream_t stream, int* sat_flag,
+                                      const float* mask, int mask_mode, float* dmask, const float* inv_scale, float* part,
+                                      size_t part_bytes, float* redscratch) {
+    if (!mask || (mask_mode != 1 && mask_mode != 2)) { set_error("bw masked attention: bad mask / mask_mode"); return TP_ERR_INVALID_ARG; }
+    const int G = grid / s, M = G * G, S2 = s * s, S2p = (S2 + 3) & ~3;
+    const long long nq = (long long)B * M;
+    const unsigned blocks = (unsigned)((nq + 3) / 4);
+    const float scale = 0.08838834764831845f;   // 1/sqrt(128)
+    float* const dpart = (dmask && mask_mode == 1) ? part : nullptr;       // mode 1: one [S2p] partial per query
+    float* const dfull = (dmask && mask_mode == 2) ? dmask : nullptr;
+    if (dpart && (size_t)nq * S2p * 4 > part_bytes) { set_error("bw masked attention: dmask partials exceed the scratch"); return TP_ERR_WORKSPACE; }
+    if (gdtype == TP_BF16)
+        hipLaunchKernelGGL((region_attention_bwd_kernel<bf16_t, true>), dim3(blocks), dim3(256), 0, stream, (const f16_t*)q,
+                           (const f16_t*)k, (const f16_t*)v, (const bf16_t*)dout, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, B, grid, s,
+                           scale, sat_flag, mask, mask_mode, dfull, dpart, S2p, inv_scale);
+    else
+        hipLaunchKernelGGL((region_attention_bwd_kernel<f16_t, true>), dim3(blocks), dim3(256), 0, stream, (const f16_t*)q,
+                           (const f16_t*)k, (const f16_t*)v, (const f16_t*)dout, (f16_t*)dq, (f16_t*)dk, (f16_t*)dv, B, grid, s,
+                           scale, sat_flag, mask, mask_mode, dfull, dpart, S2p, inv_scale);
+    if (int rc = check_launch("region_attention_bwd_kernel (masked)")) return rc;
+    if (!dpart) return TP_OK;
+    // mode 1: dmask[kk] = sum over the queries' partials — the many-parts reduction (a summation tree fixed by (nq, slices):
+    // bit-reproducible) over the padded rows, writing the S2 entries of dmask (the 1 / S of the fp16 chain already applied)
+    if (nq > INT32_MAX) { set_error("bw masked attention: too many queries"); return TP_ERR_INVALID_ARG; }
+    return bw_reduce_many_parts_launch(TP_F32, dpart, S2p, (int)nq, S2p, dmask, redscratch, stream, nullptr, S2);
 }
 
 }  // namespace tp

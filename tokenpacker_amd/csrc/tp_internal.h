@@ -400,14 +400,22 @@ int bw_colsum_rows_launch(int dtype, const void* src, long long ld, long long R,
                           float* amax_part = nullptr, int* amax_count = nullptr);
 int bw_scale_from_partials_launch(const float* amax_part, int nparts, float* scale, hipStream_t stream);
 constexpr int kReduceSlices = 32;                  // stage-1 slices of the many-parts reduction: scratch = kReduceSlices * n floats
+// (`n_out` >= 0: write only the first n_out of the n columns — n padded to a multiple of 4 for the stage-1 loads)
 int bw_reduce_many_parts_launch(int dst_dtype, const float* part, long long part_stride, int nparts, int n, void* out,
-                                float* scratch, hipStream_t stream, const float* out_scale = nullptr);
+                                float* scratch, hipStream_t stream, const float* out_scale = nullptr, int n_out = -1);
 // part: [nblocks][3][E] — dgamma, dbeta, colsum(dx) partials.  beta / xn (optional): also write the LayerNorm's output in gdtype
 int bw_ln_backward_launch(int gdtype, const void* dy, const void* x_f16, const float* mean_rstd, const float* gamma,
                           void* dx, float* part, int nblocks, long long rows, hipStream_t stream, const float* beta = nullptr,
                           void* xn = nullptr, int* sat_flag = nullptr);
 int bw_region_attention_launch(int gdtype, const void* q, const void* k, const void* v, const void* dout, void* dq,
                                void* dk, void* dv, int B, int grid, int s, hipStream_t stream, int* sat_flag = nullptr);
+// The same with the additive attn_mask (mode 1 / 2, see region_attention_launch) in the recomputed logits, and — when `dmask` is
+// non-NULL — dL/dmask in fp32, in the mask's layout, times *inv_scale (NULL: 1).  Mode 1 reduces per-query partials held in
+// `part` (needs B*M*ceil4(s*s) floats) through `redscratch` (kReduceSlices * ceil4(s*s) floats); mode 2 writes every entry once.
+int bw_region_attention_masked_launch(int gdtype, const void* q, const void* k, const void* v, const void* dout, void* dq,
+                                      void* dk, void* dv, int B, int grid, int s, hipStream_t stream, int* sat_flag,
+                                      const float* mask, int mask_mode, float* dmask, const float* inv_scale, float* part,
+                                      size_t part_bytes, float* redscratch);
 int validate_desc(const tp_desc* d);
 void pack_registry_put(const void* packed, const tp_desc* d, bool train_pack);      // tp_api.hip: what an image was packed for
 int pack_registry_check(const void* packed, const tp_desc* d, bool train);

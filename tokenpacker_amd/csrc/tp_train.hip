@@ -255,6 +255,14 @@ int tp_forward_train(const tp_desc* desc, const void* x, const int64_t x_strides
                         stream, nullptr, true);
 }
 
+int tp_forward_train_masked(const tp_desc* desc, const void* x, const int64_t x_strides[3], const void* x_multi,
+                            const void* const xm_parts[4], const int64_t xm_strides[3], const void* packed_weights, void* out,
+                            void* train_workspace, size_t workspace_bytes, const float* attn_mask, int mask_mode, void* stream) {
+    if ((mask_mode != 0 && !attn_mask) || mask_mode < 0 || mask_mode > 2) { set_error("tp_forward_train_masked: bad mask / mask_mode"); return TP_ERR_INVALID_ARG; }
+    return forward_impl(desc, x, x_strides, xm_parts ? nullptr : x_multi, xm_strides, packed_weights, out, train_workspace,
+                        workspace_bytes, stream, nullptr, true, xm_parts, mask_mode ? attn_mask : nullptr, mask_mode);
+}
+
 int tp_forward_train_parts(const tp_desc* desc, const void* x, const int64_t x_strides[3],
                            const void* const xm_parts[4], const int64_t part_strides[3], const void* packed_weights,
                            void* out, void* train_workspace, size_t workspace_bytes, void* stream) {
@@ -269,14 +277,27 @@ int tp_forward_train_parts(const tp_desc* desc, const void* x, const int64_t x_s
 static int backward_impl(const tp_desc* desc, const void* x_multi, const void* const* xm_parts, const int64_t xm_strides[3],
                          const tp_weights* raw, const void* packed_weights, const void* train_workspace, const void* dy,
                          const tp_grads* grads, void* bw_workspace, size_t bw_workspace_bytes, void* stream_,
-                         const tp_input_grads* ig = nullptr) {
+                         const tp_input_grads* ig = nullptr, const tp_attn_mask* am = nullptr) {
     tp::TuningScope tuning_scope(desc);
     TP_TRY(validate_desc(desc));
     if (xm_parts) {
         for (int i = 0; i < 4; ++i) if (!xm_parts[i]) { set_error("tp_backward: x_multi part %d is NULL", i); return TP_ERR_INVALID_ARG; }
         x_multi = xm_parts[0];
     }
-    if (!x_multi || !xm_strides || !raw || !packed_weights || !train_workspace || !dy || (!grads && !ig) || !bw_workspace) {
+    // attn_mask (tp_backward_masked): mode 1 / 2 with a mask, or mode 0 with neither a mask nor a gradient
+    const int mask_mode = am ? am->mode : 0;
+    if (am && (mask_mode < 0 || mask_mode > 2 || (mask_mode != 0) != (am->mask != nullptr) || (mask_mode == 0 && am->grad) ||
+               ((uintptr_t)am->mask & 3) || ((uintptr_t)am->grad & 3))) {
+        set_error("tp_backward_masked: bad mask (mode %d must be 1 or 2 with a 4-byte aligned mask, or 0 with no mask and no grad)",
+                  mask_mode);
+        return TP_ERR_INVALID_ARG;
+    }
+    if (am && am->reserved != 0) {                       // (kept 0 so that a later revision of ABI 6 can give it a meaning)
+        set_error("tp_backward_masked: tp_attn_mask.reserved must be 0 (got %d)", am->reserved);
+        return TP_ERR_INVALID_ARG;
+    }
+    float* const dmask = mask_mode ? am->grad : nullptr;
+    if (!x_multi || !xm_strides || !raw || !packed_weights || !train_workspace || !dy || (!grads && !ig && !dmask) || !bw_workspace) {
         set_error("tp_backward: NULL argument");
         return TP_ERR_INVALID_ARG;
     }
@@ -296,7 +317,7 @@ static int backward_impl(const tp_desc* desc, const void* x_multi, const void* c
         if (nparts != 0 && nparts != 4) { set_error("tp_backward_inputs: dx_multi_parts must be all four or none"); return TP_ERR_INVALID_ARG; }
         if (nparts && !xm_parts) { set_error("tp_backward_inputs: dx_multi_parts belong to tp_backward_inputs_parts (use dx_multi)"); return TP_ERR_INVALID_ARG; }
         if (dxm && xm_parts) { set_error("tp_backward_inputs_parts: the gradient of four x_multi sources goes to dx_multi_parts"); return TP_ERR_INVALID_ARG; }
-        if (!dx && !dxm && !nparts && !grads) { set_error("tp_backward_inputs: nothing requested (no input and no parameter gradients)"); return TP_ERR_INVALID_ARG; }
+        if (!dx && !dxm && !nparts && !grads && !dmask) { set_error("tp_backward_inputs: nothing requested (no input and no parameter gradients)"); return TP_ERR_INVALID_ARG; }
         bool aligned = ((uintptr_t)dx & 15) == 0 && ((uintptr_t)dxm & 15) == 0;
         for (int i = 0; i < 4; ++i) aligned = aligned && ((uintptr_t)dxm_parts[i] & 15) == 0;
         if (!aligned) { set_error("tp_backward_inputs: dx / dx_multi must be 16-byte aligned"); return TP_ERR_INVALID_ARG; }
@@ -473,8 +494,16 @@ static int backward_impl(const tp_desc* desc, const void* x_multi, const void* c
     }
     TP_TRY(dgrad(bw + L.da1, E, Rq, E, bw + L.wt_out, E, bw + L.dO, E));
     // ---- region attention ---------------------------------------------------------------------------------------
-    TP_TRY(bw_region_attention_launch(GT, fw + W.q, fw + W.kv, fw + W.kv + kvE * 2, bw + L.dO, bw + L.dQ, bw + L.dKV,
-                                      bw + L.dKV + kvE * 2, B, g, s, stream, sat));
+    // (masked: the mask in the recomputed logits, dL/dmask if asked for — mode 1's per-query partials in the split-K partial slab,
+    // free between two weight gradients; every head's p still sums to 1, so in_proj_bias' v third below stays colsum(dO))
+    if (mask_mode)
+        TP_TRY(bw_region_attention_masked_launch(GT, fw + W.q, fw + W.kv, fw + W.kv + kvE * 2, bw + L.dO, bw + L.dQ, bw + L.dKV,
+                                                 bw + L.dKV + kvE * 2, B, g, s, stream, sat, am->mask, mask_mode, dmask, inv_scale,
+                                                 part, L.part_bytes, redscratch));
+    else
+        TP_TRY(bw_region_attention_launch(GT, fw + W.q, fw + W.kv, fw + W.kv + kvE * 2, bw + L.dO, bw + L.dQ, bw + L.dKV,
+                                          bw + L.dKV + kvE * 2, B, g, s, stream, sat));
+    if (!pg && !ig) return TP_OK;                       // (dL/dmask only: nothing below the attention is wanted)
     // ---- attention in-projection (rows of in_proj_weight / in_proj_bias: q | k | v) --------------------------------
     char* g_inw = pg ? (char*)grads->clip_attn_in_proj_weight : nullptr;
     char* g_inb = pg ? (char*)grads->clip_attn_in_proj_bias : nullptr;
@@ -650,6 +679,15 @@ int tp_backward_inputs_parts(const tp_desc* desc, const void* const xm_parts[4],
     if (!ig) { set_error("tp_backward_inputs_parts: ig is NULL"); return TP_ERR_INVALID_ARG; }
     return backward_impl(desc, nullptr, xm_parts, part_strides, raw, packed_weights, train_workspace, dy, grads,
                          bw_workspace, bw_workspace_bytes, stream, ig);
+}
+
+int tp_backward_masked(const tp_desc* desc, const void* x_multi, const void* const xm_parts[4], const int64_t xm_strides[3],
+                       const tp_weights* raw, const void* packed_weights, const void* train_workspace, const void* dy,
+                       const tp_grads* grads, const tp_input_grads* ig, const tp_attn_mask* mask, void* bw_workspace,
+                       size_t bw_workspace_bytes, void* stream) {
+    if (!mask) { set_error("tp_backward_masked: mask is NULL"); return TP_ERR_INVALID_ARG; }
+    return backward_impl(desc, xm_parts ? nullptr : x_multi, xm_parts, xm_strides, raw, packed_weights, train_workspace, dy, grads,
+                         bw_workspace, bw_workspace_bytes, stream, ig, mask);
 }
 
 }  // extern "C"

@@ -39,31 +39,33 @@ class _ProjectFn(torch.autograd.Function):
     workspace, ``tp_backward`` returns the gradients of the 23 parameters.  The CLIP features come from a frozen
     ``no_grad`` tower in the reference's recipe (clip_encoder.py:46, train.py:950-953) and get none — unless the module's
     ``input_gradients`` switch let them in requiring grad: then ``tp_backward_inputs*`` also returns dx / dx_multi, computing
-    only what ``ctx.needs_input_grad`` asks for (no parameter gradients at all for a frozen projector)."""
+    only what ``ctx.needs_input_grad`` asks for (no parameter gradients at all for a frozen projector).  With an ``attn_mask``
+    (the device fp32 operand, ``mask_mode`` 1 / 2) the step runs ``tp_forward_train_masked`` / ``tp_backward_masked``, and a float
+    mask that requires grad — a learnable region bias, an ordinary autograd leaf in the reference — receives dL/dmask."""
 
     @staticmethod
-    def forward(ctx, module, x, n_parts, *rest):
+    def forward(ctx, module, x, mask, mask_mode, n_parts, *rest):
         xm, params = rest[:n_parts], rest[n_parts:]          # x_multi: one tensor, or its four sources
-        out, train_ws, desc, packed = module._launch_forward(x, xm[0] if n_parts == 1 else xm, train=True)
-        ctx.module, ctx.desc, ctx.n_parts = module, desc, n_parts
-        ctx.save_for_backward(train_ws, packed, *xm, *params)
+        out, train_ws, desc, packed = module._launch_forward(x, xm[0] if n_parts == 1 else xm, train=True,
+                                                             mask=None if mask is None else (mask, mask_mode))
+        ctx.module, ctx.desc, ctx.n_parts, ctx.mask_mode = module, desc, n_parts, mask_mode
+        ctx.save_for_backward(train_ws, packed, mask, *xm, *params)
         return out
 
     @staticmethod
     def backward(ctx, dy):
-        train_ws, packed, *rest = ctx.saved_tensors
+        train_ws, packed, mask, *rest = ctx.saved_tensors
         n = ctx.n_parts
         xm, params = rest[:n], rest[n:]
-        need = ctx.needs_input_grad                          # (module, x, n_parts, *x_multi, *params)
-        want_dx, want_dxm, want_params = need[1], any(need[3:3 + n]), any(need[3 + n:])
-        if not (want_dx or want_dxm):
-            grads = ctx.module._launch_backward(ctx.desc, xm[0] if n == 1 else xm, train_ws, packed, params, dy)
-            return (None, None, None) + (None,) * n + tuple(grads)
-        grads, dx, dxm = ctx.module._launch_backward(ctx.desc, xm[0] if n == 1 else xm, train_ws, packed, params, dy,
-                                                     want_params=want_params, want_dx=want_dx, want_dxm=want_dxm)
+        need = ctx.needs_input_grad                          # (module, x, mask, mask_mode, n_parts, *x_multi, *params)
+        want_dx, want_dmask, want_dxm, want_params = need[1], need[2], any(need[5:5 + n]), any(need[5 + n:])
+        grads, dx, dxm, dmask = ctx.module._launch_backward(ctx.desc, xm[0] if n == 1 else xm, train_ws, packed, params, dy,
+                                                            want_params=want_params, want_dx=want_dx, want_dxm=want_dxm,
+                                                            mask=None if mask is None else (mask, ctx.mask_mode),
+                                                            want_dmask=want_dmask)
         dxm = (dxm,) if n == 1 else (dxm or (None,) * n)
-        dxm = tuple(g if need[3 + i] else None for i, g in enumerate(dxm))
-        return (None, dx, None) + dxm + (tuple(grads) if grads is not None else (None,) * len(params))
+        dxm = tuple(g if need[5 + i] else None for i, g in enumerate(dxm))
+        return (None, dx, dmask, None, None) + dxm + (tuple(grads) if grads is not None else (None,) * len(params))
 
 
 def _forget_packed(ptr: int) -> None:
@@ -355,8 +357,11 @@ class TokenPacker(nn.Module):
                 "the HIP projector does not differentiate with respect to the CLIP features by default (the reference's tower "
                 "is frozen and runs under no_grad, clip_encoder.py:46); detach them, or set module.input_gradients = True")
         mask = self._attn_mask_operand(attn_mask, x.shape[0], x.device) if attn_mask is not None else None
-        if mask is not None and (parts or _stage_events is not None):
-            raise NotImplementedError("attn_mask takes the concatenated x_multi and no staged timing")
+        if mask is not None and _stage_events is not None:
+            raise NotImplementedError("attn_mask takes no staged timing")
+        # (a float mask that requires grad, with grad mode on: `.to()` hands back an fp32 device leaf as it is, requires_grad and
+        # all, so under no_grad its operand still says requires_grad — and that call is inference)
+        mask_grad = torch.is_grad_enabled() and mask is not None and mask[0].requires_grad
         if x.shape[0] == 0:                  # empty batch: the reference returns an empty [0, M, D] tensor
             out_dtype = torch.float32 if self.output_fp32 else x.dtype
             y = x.new_zeros((0, self.num_queries, self.hidden_size), dtype=out_dtype) if _out is None else _out
@@ -364,6 +369,8 @@ class TokenPacker(nn.Module):
                 y = y + 0.0 * sum(p.sum() for p in self.parameters() if p.requires_grad).to(out_dtype)
             if inputs_grad:                  # (connected too: their gradients come back as zeros)
                 y = y + 0.0 * sum(t.sum() for t in (x, *(parts or (x_multi,))) if t.requires_grad).to(out_dtype)
+            if mask_grad:                    # (and so is a mask that requires grad: zeros, whatever -inf it holds)
+                y = y + (mask[0] * 0.0).nan_to_num(0.0).sum().to(out_dtype)
             return y
         if x.dtype != compute_dtype:                  # autocast / fp32 caller: operands rounded once, like autocast's casts
             x = x.to(compute_dtype)
@@ -380,20 +387,22 @@ class TokenPacker(nn.Module):
             x_multi = parts
         else:
             x_multi = self._addressable(x_multi)
-        if inputs_grad or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
-            if _stage_events is not None or self.output_fp32 or fp32_caller or _out is not None or mask is not None:
-                raise NotImplementedError("staged timing / fp32 output / fp32_compute_dtype / _out / attn_mask are inference-only")
+        if inputs_grad or mask_grad or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
+            if _stage_events is not None or self.output_fp32 or fp32_caller or _out is not None:
+                raise NotImplementedError("staged timing / fp32 output / fp32_compute_dtype / _out are inference-only")
             # (partially frozen projectors — e.g. LoRA-style experiments freezing the K/V branches — go through the same
             # node: tp_backward computes every gradient, autograd drops those of parameters that do not require one)
             xm = x_multi if parts else (x_multi,)
-            return _ProjectFn.apply(self, x, len(xm), *xm, *self._named_weights())
+            return _ProjectFn.apply(self, x, None if mask is None else mask[0], 0 if mask is None else mask[1], len(xm), *xm,
+                                    *self._named_weights())
         return self._launch_forward(x, x_multi, train=False, _stage_events=_stage_events, fp32_out=fp32_caller, out=_out,
                                     mask=mask)[0]
 
     def _attn_mask_operand(self, attn_mask: torch.Tensor, B: int, device):
         """``attn_mask`` as ``nn.MultiheadAttention`` receives it from the reference's forward (builder.py:107,130): 2-D
         ``[1, s*s]`` or 3-D ``[(M*B)*num_heads, 1, s*s]`` (batch index = region * B + image, divide_feature's order),
-        boolean (True = masked out) or additive float -> ``(fp32 additive tensor on the device, mask_mode)``."""
+        boolean (True = masked out) or additive float -> ``(fp32 additive tensor on the device, mask_mode)``.  The conversion is
+        differentiable: a float leaf that requires grad gets dL/dmask back in its own dtype, shape and device."""
         S2 = self.scale_factor ** 2
         m = attn_mask
         if m.dim() == 2 and tuple(m.shape) == (1, S2):
@@ -441,7 +450,13 @@ class TokenPacker(nn.Module):
                 if ws_bytes == 0:
                     raise RuntimeError(f"tp_train_workspace_bytes: {_capi.last_error()}")
                 ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)     # lives until backward has run
-                if parts:
+                if mask is not None:             # (the training schedule writes K | V anyway: same workspace, mask or not)
+                    _capi.check(lib.tp_forward_train_masked(ctypes.byref(desc), x.data_ptr(), _capi.strides3(x.stride()),
+                                                            None if parts else x_multi.data_ptr(), part_ptrs if parts else None,
+                                                            part_strides if parts else _capi.strides3(x_multi.stride()),
+                                                            packed.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                            mask[0].data_ptr(), mask[1], stream_ptr), "tp_forward_train_masked")
+                elif parts:
                     _capi.check(lib.tp_forward_train_parts(ctypes.byref(desc), x.data_ptr(), _capi.strides3(x.stride()),
                                                            part_ptrs, part_strides, packed.data_ptr(), out.data_ptr(),
                                                            ws.data_ptr(), ws.numel(), stream_ptr), "tp_forward_train_parts")
@@ -458,7 +473,12 @@ class TokenPacker(nn.Module):
             if ws_bytes == 0:
                 raise RuntimeError(f"tp_workspace_bytes: {_capi.last_error()}")
             ws = self._workspace(ws_bytes, device, stream_ptr)
-            if parts:
+            if parts and mask is not None:
+                _capi.check(lib.tp_forward_parts_masked(ctypes.byref(desc), x.data_ptr(), _capi.strides3(x.stride()),
+                                                        part_ptrs, part_strides, packed.data_ptr(), out.data_ptr(),
+                                                        ws.data_ptr(), ws.numel(), mask[0].data_ptr(), mask[1], stream_ptr),
+                            "tp_forward_parts_masked")
+            elif parts:
                 _capi.check(lib.tp_forward_parts(ctypes.byref(desc), x.data_ptr(), _capi.strides3(x.stride()),
                                                  part_ptrs, part_strides, packed.data_ptr(), out.data_ptr(),
                                                  ws.data_ptr(), ws.numel(), stream_ptr), "tp_forward_parts")
@@ -538,10 +558,12 @@ class TokenPacker(nn.Module):
                         "tp_debug_count_saturated")
             return dict(zip(_capi.DEBUG_BUFFER_NAMES, counts.tolist()))
 
-    def _launch_backward(self, desc, x_multi, train_ws, packed, params, dy, want_params=True, want_dx=False, want_dxm=False):
-        """-> the 23 parameter gradients (tp_backward*); with ``want_dx`` / ``want_dxm`` (tp_backward_inputs*) ->
-        ``(parameter gradients or None, dx or None, dx_multi or None)`` — dx_multi one [B, N, 4096] tensor, or a tuple of the
-        four sources' [B, N, 1024] gradients when x_multi came as parts."""
+    def _launch_backward(self, desc, x_multi, train_ws, packed, params, dy, want_params=True, want_dx=False, want_dxm=False,
+                         mask=None, want_dmask=False):
+        """-> ``(parameter gradients or None, dx or None, dx_multi or None, dL/dmask or None)``, computing only what is asked for:
+        tp_backward* (parameters only), tp_backward_inputs* (``want_dx`` / ``want_dxm``) or, with the step's ``mask = (fp32 device
+        operand, mode)``, tp_backward_masked (``want_dmask``: the mask's own gradient).  dx_multi is one [B, N, 4096] tensor, or a
+        tuple of the four sources' [B, N, 1024] gradients when x_multi came as parts."""
         inputs = want_dx or want_dxm
         parts = tuple(x_multi) if isinstance(x_multi, (tuple, list)) else None
         if parts:
@@ -556,18 +578,19 @@ class TokenPacker(nn.Module):
             raw = _capi.tp_weights(*[t.data_ptr() for t in contiguous])
             grads = [torch.empty_like(t) for t in contiguous] if want_params else None
             gptr = _capi.tp_grads(*[t.data_ptr() for t in grads]) if want_params else None
+            g_arg = ctypes.byref(gptr) if want_params else None
             bw_bytes = (lib.tp_backward_inputs_workspace_bytes if inputs else lib.tp_backward_workspace_bytes)(ctypes.byref(desc))
             if bw_bytes == 0:
                 raise RuntimeError(f"tp_backward_workspace_bytes: {_capi.last_error()}")
             bw = self._workspace(bw_bytes, device, ("bwd", stream_ptr))
             dy = dy.to(x_multi.dtype).contiguous()
+            dx = dxm = ig = dmask = None
             if inputs:
                 B, N, E = desc.batch, self.raw_grid * self.raw_grid, self.embed_dim
                 new = partial(torch.empty, dtype=x_multi.dtype, device=device)
                 dx = new(B, N, E) if want_dx else None
                 ig = _capi.tp_input_grads()
                 ig.dx = dx.data_ptr() if want_dx else None
-                dxm = None
                 if want_dxm and parts:
                     dxm = tuple(new(B, N, self.MULTI_LEVEL_DIM // 4) for _ in range(4))
                     for i, t in enumerate(dxm):
@@ -575,34 +598,37 @@ class TokenPacker(nn.Module):
                 elif want_dxm:
                     dxm = new(B, N, self.MULTI_LEVEL_DIM)
                     ig.dx_multi = dxm.data_ptr()
-                g_arg = ctypes.byref(gptr) if want_params else None
-                if parts:
-                    part_ptrs = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in parts])
-                    _capi.check(lib.tp_backward_inputs_parts(ctypes.byref(desc), part_ptrs, _capi.strides3(parts[0].stride()),
-                                                             ctypes.byref(raw), packed.data_ptr(), train_ws.data_ptr(),
-                                                             dy.data_ptr(), g_arg, ctypes.byref(ig), bw.data_ptr(), bw.numel(),
-                                                             stream_ptr), "tp_backward_inputs_parts")
-                else:
-                    _capi.check(lib.tp_backward_inputs(ctypes.byref(desc), x_multi.data_ptr(), _capi.strides3(x_multi.stride()),
-                                                       ctypes.byref(raw), packed.data_ptr(), train_ws.data_ptr(), dy.data_ptr(),
-                                                       g_arg, ctypes.byref(ig), bw.data_ptr(), bw.numel(), stream_ptr),
-                                "tp_backward_inputs")
-                self._watch_backward_status(bw, device)
-                if grads is not None:
-                    grads = [g if g.dtype == p.dtype else g.to(p.dtype) for g, p in zip(grads, params)]
-                return grads, dx, dxm
-            if parts:
-                part_ptrs = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in parts])
-                _capi.check(lib.tp_backward_parts(ctypes.byref(desc), part_ptrs, _capi.strides3(parts[0].stride()),
-                                                  ctypes.byref(raw), packed.data_ptr(), train_ws.data_ptr(), dy.data_ptr(),
-                                                  ctypes.byref(gptr), bw.data_ptr(), bw.numel(), stream_ptr),
-                            "tp_backward_parts")
+            part_ptrs = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in parts]) if parts else None
+            xm_strides = _capi.strides3((parts[0] if parts else x_multi).stride())
+            if mask is not None:
+                dmask = torch.empty_like(mask[0]) if want_dmask else None
+                am = _capi.tp_attn_mask(mask=mask[0].data_ptr(), mode=mask[1], reserved=0,
+                                        grad=dmask.data_ptr() if want_dmask else None)
+                _capi.check(lib.tp_backward_masked(ctypes.byref(desc), None if parts else x_multi.data_ptr(), part_ptrs,
+                                                   xm_strides, ctypes.byref(raw), packed.data_ptr(), train_ws.data_ptr(),
+                                                   dy.data_ptr(), g_arg, ctypes.byref(ig) if inputs else None, ctypes.byref(am),
+                                                   bw.data_ptr(), bw.numel(), stream_ptr), "tp_backward_masked")
+            elif inputs and parts:
+                _capi.check(lib.tp_backward_inputs_parts(ctypes.byref(desc), part_ptrs, xm_strides, ctypes.byref(raw),
+                                                         packed.data_ptr(), train_ws.data_ptr(), dy.data_ptr(), g_arg,
+                                                         ctypes.byref(ig), bw.data_ptr(), bw.numel(), stream_ptr),
+                            "tp_backward_inputs_parts")
+            elif inputs:
+                _capi.check(lib.tp_backward_inputs(ctypes.byref(desc), x_multi.data_ptr(), xm_strides, ctypes.byref(raw),
+                                                   packed.data_ptr(), train_ws.data_ptr(), dy.data_ptr(), g_arg, ctypes.byref(ig),
+                                                   bw.data_ptr(), bw.numel(), stream_ptr), "tp_backward_inputs")
+            elif parts:
+                _capi.check(lib.tp_backward_parts(ctypes.byref(desc), part_ptrs, xm_strides, ctypes.byref(raw), packed.data_ptr(),
+                                                  train_ws.data_ptr(), dy.data_ptr(), g_arg, bw.data_ptr(), bw.numel(),
+                                                  stream_ptr), "tp_backward_parts")
             else:
-                _capi.check(lib.tp_backward(ctypes.byref(desc), x_multi.data_ptr(), _capi.strides3(x_multi.stride()),
-                                            ctypes.byref(raw), packed.data_ptr(), train_ws.data_ptr(), dy.data_ptr(),
-                                            ctypes.byref(gptr), bw.data_ptr(), bw.numel(), stream_ptr), "tp_backward")
+                _capi.check(lib.tp_backward(ctypes.byref(desc), x_multi.data_ptr(), xm_strides, ctypes.byref(raw),
+                                            packed.data_ptr(), train_ws.data_ptr(), dy.data_ptr(), g_arg, bw.data_ptr(),
+                                            bw.numel(), stream_ptr), "tp_backward")
             self._watch_backward_status(bw, device)
-        return [g if g.dtype == p.dtype else g.to(p.dtype) for g, p in zip(grads, params)]
+        if grads is not None:
+            grads = [g if g.dtype == p.dtype else g.to(p.dtype) for g, p in zip(grads, params)]
+        return grads, dx, dxm, dmask
 
     def backward_saturated(self) -> int:
         """The sticky saturation word of the LAST backward on the current stream's workspace (include/tokenpacker.h: bit 0 a

@@ -186,3 +186,13 @@ def make_attn_masks(seed: int, B: int, s: int, raw_grid: int = RAW_GRID):
     m3 = torch.rand(M * B * N_HEADS, 1, S2, generator=g) < 0.35
     m3[:, 0, 0] = False
     return m2, m3
+
+
+def make_train_attn_masks(seed: int, B: int, s: int, raw_grid: int = RAW_GRID) -> dict:
+    """The three masks training with an attn_mask is checked on (tools/make_mask_grad_golden.py, tests/test_*mask_train*):
+    ``make_attn_masks``' 2-D float ``[1, s*s]`` and 3-D boolean forms, and a 3-D additive float mask ``[(M*B)*8, 1, s*s]``
+    (1.5 x unit normal) — the two float ones are what a learnable region bias looks like."""
+    m2, m3 = make_attn_masks(seed, B, s, raw_grid)
+    M = (raw_grid // s) ** 2
+    m3f = 1.5 * torch.randn(M * B * N_HEADS, 1, s * s, generator=torch.Generator().manual_seed(seed + 1))
+    return {"2d_float": m2, "3d_bool": m3, "3d_float": m3f}

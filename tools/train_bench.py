@@ -11,6 +11,9 @@ backward actually has to do: no input gradient for k/v_proj_1[0] (the CLIP featu
 
 --input-grads also times the step with the opt-in gradients with respect to x and x_multi (module.input_gradients, both
 inputs requiring grad) and prices the two extra dgrads: dx_multi = dZ1 · [Wk0; Wv0] and dq0 = dQ1pre · Wq1.
+--mask also times the step with an attn_mask that is a learnable region bias (a float mask requiring grad: the masked attention
+backward and dL/dmask): the 2-D [1, s*s] form (dmask summed over every image, query and head) and the 3-D [(M*B)*8, 1, s*s]
+form (every entry written once).
 """
 import argparse
 import json
@@ -64,6 +67,7 @@ def main():
     ap.add_argument("--hip-only", action="store_true", help="skip the eager baseline (profiling runs)")
     ap.add_argument("--optimizer", default="sgd", choices=["sgd", "none"])
     ap.add_argument("--input-grads", action="store_true", help="also time the step with gradients with respect to x / x_multi")
+    ap.add_argument("--mask", action="store_true", help="also time the step with a learnable attn_mask (2-D and 3-D float)")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE", help="library tuning knob, e.g. BWD_CHAIN=1")
     args = ap.parse_args()
     from tokenpacker_amd import _capi
@@ -112,14 +116,32 @@ def main():
             if opt is not None:
                 opt.step()
 
+        S2, M = s * s, (24 // s) ** 2
+        masks = {}                                        # (built only when asked for: they draw from the same generator)
+        if args.mask:
+            masks = {"2d": (0.5 * torch.randn(1, S2, generator=g, device="cuda")).requires_grad_(True),
+                     "3d": (0.5 * torch.randn(M * B * 8, 1, S2, generator=g, device="cuda")).requires_grad_(True)}
+
+        def step_hip_mask(mask):
+            m.zero_grad(set_to_none=True)
+            mask.grad = None
+            (m((x, xm), attn_mask=mask) * w).sum().backward()
+            if opt is not None:
+                opt.step()
+
         iters = 20 if B <= 64 else 8
         ms_hip = timed(step_hip, iters)
         ig = {}
+        if args.mask:
+            for kind, mask in masks.items():
+                ms_mask = timed(lambda: step_hip_mask(mask), iters)
+                ig.update({f"hip_fwd_bwd_mask_{kind}_ms": round(ms_mask, 3), f"mask_{kind}_extra_ms": round(ms_mask - ms_hip, 3)})
+                mask.grad = None
         if args.input_grads:
             ms_in = timed(step_hip_inputs, iters)
-            ig = {"hip_fwd_bwd_input_grads_ms": round(ms_in, 3), "input_grads_extra_ms": round(ms_in - ms_hip, 3),
-                  "input_grads_extra_gflop": round(flops_input_grads(B, s) / 1e9, 1),
-                  "input_grads_extra_tflops": round(flops_input_grads(B, s) / max(ms_in - ms_hip, 1e-6) / 1e9, 1)}
+            ig.update({"hip_fwd_bwd_input_grads_ms": round(ms_in, 3), "input_grads_extra_ms": round(ms_in - ms_hip, 3),
+                       "input_grads_extra_gflop": round(flops_input_grads(B, s) / 1e9, 1),
+                       "input_grads_extra_tflops": round(flops_input_grads(B, s) / max(ms_in - ms_hip, 1e-6) / 1e9, 1)})
             x_in.grad = xm_in.grad = None
         ms_eager = timed(step_eager, iters) if not args.hip_only else float("nan")
         ms_fwd = timed(fwd_hip, iters)
@@ -130,7 +152,7 @@ def main():
             rec = {"B": B, "hip_fwd_bwd_ms": round(ms_hip, 3), "hip_fwd_only_ms": round(ms_fwd, 3), **ig}
             print(json.dumps(rec), flush=True)
             results.append(rec)
-            del m, x, xm, w, x_in, xm_in
+            del m, x, xm, w, x_in, xm_in, masks
             torch.cuda.empty_cache()
             continue
         finite = {"hip": all(bool(torch.isfinite(p.float()).all()) for p in m.parameters()),
@@ -153,7 +175,7 @@ def main():
                "weights_finite_after_training": finite, "max_param_grad_rel_l2_vs_eager": agree, "tune": args.tune, **ig}
         print(json.dumps(rec), flush=True)
         results.append(rec)
-        del m, m_eager, x, xm, w, x_in, xm_in
+        del m, m_eager, x, xm, w, x_in, xm_in, masks
         torch.cuda.empty_cache()
     os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
     json.dump(results, open(args.out, "w"), indent=1)
