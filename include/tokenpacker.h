@@ -430,7 +430,18 @@ int tp_wgrad(const void* dy, int64_t ldy, const void* x, int64_t ldx, int x_rows
  * already in place (llava_arch.py:172-191) — the visual tokens then land where the LLM reads them.
  * `crop_map` (device int32[n_crops], or NULL): logical crop c lives in row block crop_map[c] of `tokens` — lets the
  * kernel read the b_max-strided buffer of a RAGGED all-gather in place (tokenpacker_amd.shard.GatheredTokens); the
- * caller guarantees the mapped blocks exist (values are not readable from the host side). */
+ * caller guarantees the mapped blocks exist (values are not readable from the host side).
+ *
+ * tp_hd_assemble_backward is its transpose, for training (the same plan, M, D, dtype and crop_map conventions):
+ * from dout [out_rows, D] it writes
+ *   dtokens [n_token_crops, M, D], the WHOLE buffer: every crop row that a block reads gets its dout row (a copy, bit-exact);
+ *     every other row is zero (crops no image reads, e.g. those of image-less samples, and unmapped slots of a ragged gather);
+ *   dsep [D] / dret [D]: the sums of dout over all ',' rows / all '\n' rows of every image of the call, accumulated in fp32
+ *     in a fixed order (no atomics: two runs give identical bits) and rounded once to `dtype`.
+ * Without crop_map, logical crop c is block c (n_token_crops >= n_crops); with it, the map must be injective and its values
+ * inside [0, n_token_crops) (entries outside are ignored).  Enqueues only: no host synchronisation, no allocation; the
+ * fp32 partials live in `workspace` (16-byte aligned) of tp_hd_assemble_backward_workspace_bytes(n_images, n_token_crops, D)
+ * bytes.  Any number of images (launches of 64). */
 typedef struct tp_hd_image {
     int32_t first_crop;
     int32_t h_block;
@@ -441,6 +452,10 @@ typedef struct tp_hd_image {
 int64_t tp_hd_rows(int h_block, int w_block, int M);
 int tp_hd_assemble(const tp_hd_image* plan, int n_images, const void* tokens, int64_t n_crops, const int32_t* crop_map,
                    const void* sep, const void* ret, void* out, int64_t out_rows, int M, int D, int dtype, void* stream);
+size_t tp_hd_assemble_backward_workspace_bytes(int n_images, int64_t n_token_crops, int D);
+int tp_hd_assemble_backward(const tp_hd_image* plan, int n_images, const void* dout, int64_t out_rows, int64_t n_crops,
+                            const int32_t* crop_map, void* dtokens, int64_t n_token_crops, void* dsep, void* dret, int M, int D,
+                            int dtype, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- TokenPacker-HD image slicing (the step before the CLIP tower) ---------------------------------------------
  * Replaces the resize / zero-pad / tile code of the data loader and the eval drivers (llava/train/train.py:695-731):

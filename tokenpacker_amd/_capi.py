@@ -59,6 +59,7 @@ EXPORTED_SYMBOLS = (
     "tp_get_tuning", "tp_release_stream",
     "tp_backward_inputs_workspace_bytes", "tp_backward_inputs", "tp_backward_inputs_parts",
     "tp_forward_train_masked", "tp_forward_parts_masked", "tp_backward_masked",
+    "tp_hd_assemble_backward_workspace_bytes", "tp_hd_assemble_backward",
     "tp_tuning_create", "tp_tuning_destroy", "tp_tuning_set", "tp_tuning_get", "tp_gather_alloc_flags", "tp_gather_free_flags", "tp_gather_export", "tp_gather_open", "tp_gather_close", "tp_gather_push", "tp_gather_sync",
 )
 # include/tokenpacker_test.h: the stateless test hooks — libtokenpacker_exp.so only (load_test_library()), never the product library
@@ -258,6 +259,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.tp_hd_assemble.restype = c_int
     lib.tp_hd_assemble.argtypes = [POINTER(tp_hd_image), c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_int64, c_int, c_int, c_int, c_void_p]
+    lib.tp_hd_assemble_backward_workspace_bytes.restype = c_size_t
+    lib.tp_hd_assemble_backward_workspace_bytes.argtypes = [c_int, c_int64, c_int]
+    lib.tp_hd_assemble_backward.restype = c_int
+    lib.tp_hd_assemble_backward.argtypes = [POINTER(tp_hd_image), c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64,
+                                            c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]
 
     if lib.tp_version() != TP_ABI_VERSION:
         raise TokenPackerLibraryError(

@@ -571,6 +571,27 @@ int64_t tp_hd_rows(int h_block, int w_block, int M) {
     return n * (M + 1) + (n > 1 ? M + 1 : 0);
 }
 
+// Images come in order; their crop ranges and output row ranges must not overlap and must lie inside
+// tokens [n_crops, M, D] / out [out_rows, D].  GAPS between the output ranges are allowed and left untouched (the
+// text embeddings of inputs_embeds live there, llava_arch.py:172-191); gaps in the crop list are allowed too.
+static int validate_hd_plan(const char* what, const tp_hd_image* plan, int n_images, int64_t n_crops, int64_t out_rows, int M) {
+    int64_t crop = 0, row = 0;
+    for (int i = 0; i < n_images; ++i) {
+        if (plan[i].h_block < 1 || plan[i].w_block < 1 || plan[i].first_crop < crop || plan[i].out_row < row) {
+            set_error("%s: plan entry %d is inconsistent (overlaps its predecessor or is out of order)", what, i);
+            return TP_ERR_INVALID_ARG;
+        }
+        crop = (int64_t)plan[i].first_crop + plan[i].h_block * plan[i].w_block + (plan[i].h_block * plan[i].w_block > 1 ? 1 : 0);
+        row = plan[i].out_row + tp_hd_rows(plan[i].h_block, plan[i].w_block, M);
+        if (crop > n_crops || row > out_rows) {
+            set_error("%s: plan entry %d reads crops up to %lld of %lld / writes rows up to %lld of %lld", what, i,
+                      (long long)crop, (long long)n_crops, (long long)row, (long long)out_rows);
+            return TP_ERR_INVALID_ARG;
+        }
+    }
+    return TP_OK;
+}
+
 int tp_hd_assemble(const tp_hd_image* plan, int n_images, const void* tokens, int64_t n_crops, const int32_t* crop_map,
                    const void* sep, const void* ret, void* out, int64_t out_rows, int M, int D, int dtype, void* stream) {
     if (!plan || !tokens || !sep || !ret || !out || n_images <= 0 || M <= 0 || n_crops <= 0 || out_rows <= 0) {
@@ -582,24 +603,46 @@ int tp_hd_assemble(const tp_hd_image* plan, int n_images, const void* tokens, in
         set_error("tp_hd_assemble: D must be a multiple of 8 and every pointer 16-byte aligned");
         return TP_ERR_INVALID_ARG;
     }
-    // Images come in order; their crop ranges and output row ranges must not overlap and must lie inside
-    // tokens [n_crops, M, D] / out [out_rows, D].  GAPS between the output ranges are allowed and left untouched (the
-    // text embeddings of inputs_embeds live there, llava_arch.py:172-191); gaps in the crop list are allowed too.
-    int64_t crop = 0, row = 0;
-    for (int i = 0; i < n_images; ++i) {
-        if (plan[i].h_block < 1 || plan[i].w_block < 1 || plan[i].first_crop < crop || plan[i].out_row < row) {
-            set_error("tp_hd_assemble: plan entry %d is inconsistent (overlaps its predecessor or is out of order)", i);
-            return TP_ERR_INVALID_ARG;
-        }
-        crop = (int64_t)plan[i].first_crop + plan[i].h_block * plan[i].w_block + (plan[i].h_block * plan[i].w_block > 1 ? 1 : 0);
-        row = plan[i].out_row + tp_hd_rows(plan[i].h_block, plan[i].w_block, M);
-        if (crop > n_crops || row > out_rows) {
-            set_error("tp_hd_assemble: plan entry %d reads crops up to %lld of %lld / writes rows up to %lld of %lld", i,
-                      (long long)crop, (long long)n_crops, (long long)row, (long long)out_rows);
-            return TP_ERR_INVALID_ARG;
-        }
-    }
+    TP_TRY(validate_hd_plan("tp_hd_assemble", plan, n_images, n_crops, out_rows, M));
     return hd_assemble_launch(plan, n_images, tokens, crop_map, sep, ret, out, M, D, (hipStream_t)stream);
+}
+
+size_t tp_hd_assemble_backward_workspace_bytes(int n_images, int64_t n_token_crops, int D) {
+    if (n_images <= 0 || n_token_crops <= 0 || D <= 0) return 0;
+    return hd_assemble_bwd_workspace_bytes(n_images, n_token_crops, D);
+}
+
+int tp_hd_assemble_backward(const tp_hd_image* plan, int n_images, const void* dout, int64_t out_rows, int64_t n_crops,
+                            const int32_t* crop_map, void* dtokens, int64_t n_token_crops, void* dsep, void* dret, int M, int D,
+                            int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!plan || !dout || !dtokens || !dsep || !dret || !workspace || n_images <= 0 || M <= 0 || n_crops <= 0 || out_rows <= 0 ||
+        n_token_crops <= 0) {
+        set_error("tp_hd_assemble_backward: NULL / non-positive argument");
+        return TP_ERR_INVALID_ARG;
+    }
+    if (dtype != TP_BF16 && dtype != TP_F16) { set_error("tp_hd_assemble_backward: dtype %d unsupported", dtype); return TP_ERR_INVALID_ARG; }
+    if (D <= 0 || D % 8 != 0 || ((uintptr_t)dout & 15) || ((uintptr_t)dtokens & 15) || ((uintptr_t)dsep & 15) || ((uintptr_t)dret & 15) ||
+        ((uintptr_t)workspace & 15)) {
+        set_error("tp_hd_assemble_backward: D must be a multiple of 8 and every pointer 16-byte aligned");
+        return TP_ERR_INVALID_ARG;
+    }
+    if (!crop_map && n_token_crops < n_crops) {
+        set_error("tp_hd_assemble_backward: without a crop map dtokens needs n_crops = %lld blocks, not %lld", (long long)n_crops,
+                  (long long)n_token_crops);
+        return TP_ERR_INVALID_ARG;
+    }
+    if (n_token_crops * M > 0x7fffffffLL) {
+        set_error("tp_hd_assemble_backward: %lld token rows exceed one launch", (long long)(n_token_crops * M));
+        return TP_ERR_INVALID_ARG;
+    }
+    TP_TRY(validate_hd_plan("tp_hd_assemble_backward", plan, n_images, n_crops, out_rows, M));
+    const size_t need = hd_assemble_bwd_workspace_bytes(n_images, n_token_crops, D);
+    if (workspace_bytes < need) {
+        set_error("tp_hd_assemble_backward: workspace %zu B < %zu B", workspace_bytes, need);
+        return TP_ERR_WORKSPACE;
+    }
+    return hd_assemble_bwd_launch(plan, n_images, dout, crop_map, dtokens, n_token_crops, dsep, dret, M, D, dtype, workspace,
+                                  (hipStream_t)stream);
 }
 
 int tp_ln_finalize(const float* row_stats, int parts, int64_t M, int ln_dim, float eps, float* row_mean_rstd, void* stream) {

@@ -243,6 +243,10 @@ int hd_slice_launch(const float* img, int H, int W, int h_block, int w_block, in
 int occupy_cus_launch(int blocks, int usec, int* sink, hipStream_t stream);
 int hd_assemble_launch(const tp_hd_image* plan_host, int n_images, const void* tokens, const int32_t* crop_map, const void* sep,
                        const void* ret, void* out, int M, int D, hipStream_t stream);
+size_t hd_assemble_bwd_workspace_bytes(int n_images, long long n_token_crops, int D);
+int hd_assemble_bwd_launch(const tp_hd_image* plan_host, int n_images, const void* dout, const int32_t* crop_map, void* dtokens,
+                           long long n_token_crops, void* dsep, void* dret, int M, int D, int dtype, void* workspace,
+                           hipStream_t stream);
 int ln_finalize_launch(const float* parts, float* mean_rstd, long long M, int nparts, int groups, int ln_dim,
                        float eps, hipStream_t stream, bool second_moment = false, bool pair_rstd = false);
 int pack_cast_f32_launch(int dtype, const void* src, float* dst, int n, hipStream_t stream);

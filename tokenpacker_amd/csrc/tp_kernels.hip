@@ -574,6 +574,117 @@ int hd_assemble_launch(const tp_hd_image* plan, int n_images, const void* tokens
     return TP_OK;
 }
 
+// Backward of the assembly (its transpose), dout [out_rows, D] ->
+//   dtokens [n_token_crops, M, D]: every crop row that a block reads gets its dout row (a copy); every other row is zero;
+//   dsep / dret [D]: the sums of dout over the ',' rows and over the '\n' rows of every image, in fp32, rounded once.
+// No atomics; every sum runs in a fixed order.  Workspace: src_row int64 [n_token_crops] | part fp32 [n_images][2][D].
+//   1. src_row[*] = -1 (memset);
+//   2. per launch of <= 64 images, one workgroup per image: src_row[token block of crop c] = the dout row of the crop's
+//      first token, and part[image] = the fp32 sums of the image's ',' rows and '\n' rows in row order;
+//   3. one workgroup per dtokens row (b, k): dout[src_row[b] + k], or zero when src_row[b] < 0;
+//   4. dsep / dret = the per-image partials summed in image order.
+template <typename T>
+__device__ __forceinline__ void hd_acc8(float* acc, const uint4 v) {
+    using X8 = typename Vec<T>::x8;
+    const X8 x = __builtin_bit_cast(X8, v);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] += (float)x[j];
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+hd_assemble_bwd_plan_kernel(const HdPlan plan, const uint4* __restrict__ dout, const int* __restrict__ crop_map,
+                            long long n_token_crops, long long* __restrict__ src_row, float* __restrict__ part, int M, int vecs) {
+    const tp_hd_image im = plan.img[blockIdx.x];
+    const int n = im.h_block * im.w_block, seg_rows = M + 1, n_crops = n + (n > 1 ? 1 : 0);
+    for (int s = threadIdx.x; s < n_crops; s += blockDim.x) {
+        const int c = im.first_crop + s;
+        const long long b = crop_map ? (long long)crop_map[c] : (long long)c;
+        if (b >= 0 && b < n_token_crops) src_row[b] = im.out_row + (long long)s * seg_rows;   // (the global view: s == n)
+    }
+    float* dst = part + (long long)blockIdx.x * 2 * vecs * 8;
+    for (int v = threadIdx.x; v < vecs; v += blockDim.x) {
+        float acc_sep[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, acc_ret[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int s = 0; s < n; ++s) {
+            const uint4 x = dout[(im.out_row + (long long)s * seg_rows + M) * vecs + v];
+            hd_acc8<T>(s % im.w_block == im.w_block - 1 ? acc_ret : acc_sep, x);
+        }
+        if (n > 1) hd_acc8<T>(acc_ret, dout[(im.out_row + (long long)n * seg_rows + M) * vecs + v]);
+        float4* ds = reinterpret_cast<float4*>(dst + v * 8);
+        float4* dr = reinterpret_cast<float4*>(dst + (vecs + v) * 8);
+        ds[0] = make_float4(acc_sep[0], acc_sep[1], acc_sep[2], acc_sep[3]);
+        ds[1] = make_float4(acc_sep[4], acc_sep[5], acc_sep[6], acc_sep[7]);
+        dr[0] = make_float4(acc_ret[0], acc_ret[1], acc_ret[2], acc_ret[3]);
+        dr[1] = make_float4(acc_ret[4], acc_ret[5], acc_ret[6], acc_ret[7]);
+    }
+}
+
+__global__ void __launch_bounds__(256)
+hd_assemble_bwd_tokens_kernel(const uint4* __restrict__ dout, const long long* __restrict__ src_row, uint4* __restrict__ dtokens,
+                              int M, int vecs) {
+    const long long row = blockIdx.x, b = row / M, k = row - b * M;
+    const long long s = src_row[b];
+    uint4* dst = dtokens + row * vecs;
+    if (s < 0) {
+        for (int v = threadIdx.x; v < vecs; v += blockDim.x) dst[v] = make_uint4(0u, 0u, 0u, 0u);
+    } else {
+        const uint4* src = dout + (s + k) * vecs;
+        for (int v = threadIdx.x; v < vecs; v += blockDim.x) dst[v] = src[v];
+    }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+hd_assemble_bwd_sum_kernel(const float* __restrict__ part, int n_images, uint4* __restrict__ dsep, uint4* __restrict__ dret, int vecs) {
+    using X8 = typename Vec<T>::x8;
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= 2 * vecs) return;                    // v < vecs: dsep, else dret
+    const long long stride = 2LL * vecs * 8;
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < n_images; ++i) {
+        const float4* p = reinterpret_cast<const float4*>(part + i * stride + (long long)v * 8);
+        const float4 a = p[0], b = p[1];
+        acc[0] += a.x; acc[1] += a.y; acc[2] += a.z; acc[3] += a.w;
+        acc[4] += b.x; acc[5] += b.y; acc[6] += b.z; acc[7] += b.w;
+    }
+    X8 out;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) out[j] = (T)acc[j];
+    (v < vecs ? dsep : dret)[v < vecs ? v : v - vecs] = __builtin_bit_cast(uint4, out);
+}
+
+size_t hd_assemble_bwd_workspace_bytes(int n_images, long long n_token_crops, int D) {
+    return (((size_t)n_token_crops * sizeof(long long) + 255) & ~(size_t)255) + (size_t)n_images * 2 * D * sizeof(float);
+}
+
+int hd_assemble_bwd_launch(const tp_hd_image* plan, int n_images, const void* dout, const int32_t* crop_map, void* dtokens,
+                           long long n_token_crops, void* dsep, void* dret, int M, int D, int dtype, void* workspace,
+                           hipStream_t stream) {
+    const int vecs = D / 8;
+    long long* src_row = (long long*)workspace;
+    float* part = (float*)((char*)workspace + hd_assemble_bwd_workspace_bytes(0, n_token_crops, D));
+    hipError_t e = hipMemsetAsync(src_row, 0xff, (size_t)n_token_crops * sizeof(long long), stream);
+    if (e != hipSuccess) { set_error("hd_assemble_bwd: hipMemsetAsync: %s", hipGetErrorString(e)); return TP_ERR_LAUNCH; }
+    auto plan_kernel = dtype == TP_BF16 ? hd_assemble_bwd_plan_kernel<bf16_t> : hd_assemble_bwd_plan_kernel<f16_t>;
+    for (int base = 0; base < n_images; base += 64) {
+        HdPlan hp{};
+        hp.n = n_images - base < 64 ? n_images - base : 64;
+        for (int i = 0; i < hp.n; ++i) hp.img[i] = plan[base + i];
+        hipLaunchKernelGGL(plan_kernel, dim3((unsigned)hp.n), dim3(256), 0, stream, hp, (const uint4*)dout, (const int*)crop_map,
+                           n_token_crops, src_row, part + (long long)base * 2 * D, M, vecs);
+        const int rc = check_launch("hd_assemble_bwd_plan_kernel");
+        if (rc != TP_OK) return rc;
+    }
+    hipLaunchKernelGGL(hd_assemble_bwd_tokens_kernel, dim3((unsigned)(n_token_crops * M)), dim3(256), 0, stream, (const uint4*)dout,
+                       (const long long*)src_row, (uint4*)dtokens, M, vecs);
+    int rc = check_launch("hd_assemble_bwd_tokens_kernel");
+    if (rc != TP_OK) return rc;
+    auto sum_kernel = dtype == TP_BF16 ? hd_assemble_bwd_sum_kernel<bf16_t> : hd_assemble_bwd_sum_kernel<f16_t>;
+    hipLaunchKernelGGL(sum_kernel, dim3((unsigned)((2 * vecs + 255) / 256)), dim3(256), 0, stream, (const float*)part, n_images,
+                       (uint4*)dsep, (uint4*)dret, vecs);
+    return check_launch("hd_assemble_bwd_sum_kernel");
+}
+
 // ---------------------------------------------------------------------------------------------------
 // TokenPacker-HD image slicing (reference llava/train/train.py:695-731, duplicated in the eval drivers): the
 // normalised image [3, H, W] is resized (bilinear, align_corners = False, no antialias — F.interpolate's

@@ -8,6 +8,9 @@
   with the ``'\\n'`` embedding.  The reference builds this with a Python loop and one ``torch.cat`` per image;
   here ONE kernel launch (``tp_hd_assemble``) writes all images of the batch straight into one
   ``[rows, D]`` buffer, of which per-image views are returned.  Device tensors only, no CPU fallback.
+* :func:`build_inputs_embeds`, :func:`build_multimodal_inputs` — the whole slice branch (embeddings, labels, attention
+  mask); differentiable with respect to the projector output and the embedding table (``tp_hd_assemble_backward``), so
+  a TokenPacker-HD training step runs through them too.
 """
 from __future__ import annotations
 
@@ -116,17 +119,16 @@ def assemble_hd_tokens(image_features: torch.Tensor, h_block: Sequence[int], w_b
     — the b_max-strided buffer of a ragged all-gather (``shard.GatheredTokens.buf`` / ``.crop_map()``) is read in
     place instead of being compacted first.
 
-    INFERENCE ONLY: the blocks are written by a raw-pointer HIP kernel autograd never sees — with a gradient live on
-    ``image_features`` (or on the separator embeddings) the call raises instead of silently cutting the graph between
-    the projector and the LLM (the reference's slice branch also runs in training; use its torch.cat form there)."""
+    Differentiable with respect to ``image_features``, ``sep_embed`` and ``ret_embed``: with a gradient live on any of
+    them (or on ``out``) the launch is an autograd node whose backward is ``tp_hd_assemble_backward`` — dL/dfeatures is a
+    copy of the incoming rows (zero for crops no block reads), dL/dsep and dL/dret are fp32 sums in a fixed order.  With
+    ``out`` it behaves like the in-place ``out[block rows] = block``: ``out``'s earlier content gets the incoming gradient
+    with the block rows zeroed.  A ``crop_map`` is then copied to the host once and must be injective (``ValueError``).
+    Nothing live (``torch.no_grad()`` or no input requiring grad): one launch, no synchronisation."""
     if not image_features.is_cuda:
         raise RuntimeError("assemble_hd_tokens runs only on an AMD GPU (HIP kernel); there is no CPU fallback")
-    if torch.is_grad_enabled() and (image_features.requires_grad or sep_embed.requires_grad or ret_embed.requires_grad
-                                    or (out is not None and out.requires_grad)):
-        raise NotImplementedError(
-            "assemble_hd_tokens / build_inputs_embeds write the visual tokens with a HIP kernel outside autograd: with a "
-            "gradient live on the projector output (or the separator embeddings / the destination buffer) the graph would "
-            "be cut silently.  Call it under torch.no_grad() (inference), or assemble with torch ops when training.")
+    live = torch.is_grad_enabled() and (image_features.requires_grad or sep_embed.requires_grad or ret_embed.requires_grad
+                                        or (out is not None and out.requires_grad))
     if image_features.dim() != 3:
         raise ValueError("image_features must be [n_crops, M, D]")
     if len(h_block) != len(w_block):
@@ -174,14 +176,80 @@ def assemble_hd_tokens(image_features: torch.Tensor, h_block: Sequence[int], w_b
             raise ValueError(f"out must be a contiguous [rows, {D}] {feats.dtype} tensor on {feats.device}")
         if row > out.shape[0]:
             raise ValueError(f"the last image's block ends at row {row}, out has {out.shape[0]} rows")
+    spec = _AssembleSpec(plan, len(h_block), n_crops, crop_map, spans, M, D, dt)
+    if not live:
+        _assemble_launch(spec, feats, sep, ret, out)
+        return [out[a:a + n] for a, n in spans]
+    if out is not None and out.is_leaf and out.requires_grad:
+        raise RuntimeError("a leaf Variable that requires grad is being used in an in-place operation (out=)")
+    if crop_map is not None:
+        cm = crop_map.cpu()
+        if int(cm.min()) < 0 or int(cm.max()) >= feats.shape[0]:
+            raise ValueError(f"crop_map values must lie in [0, {feats.shape[0]})")
+        if torch.unique(cm).numel() != cm.numel():
+            raise ValueError("crop_map must be injective when a gradient is live (two crops would share one gradient row)")
+    out = _AssembleFn.apply(feats, sep, ret, out, spec)
+    return [out[a:a + n] for a, n in spans]
+
+
+class _AssembleSpec:
+    """What one tp_hd_assemble call and its backward share: the host plan and the shapes."""
+
+    def __init__(self, plan, n_images, n_crops, crop_map, spans, M, D, dt):
+        self.plan, self.n_images, self.n_crops, self.crop_map = plan, n_images, n_crops, crop_map
+        self.spans, self.M, self.D, self.dt = spans, M, D, dt
+
+
+def _assemble_launch(spec: _AssembleSpec, feats, sep, ret, out) -> None:
     lib = _capi.load_library()
     with torch.cuda.device(feats.device):
-        _capi.check(lib.tp_hd_assemble(plan, len(h_block), feats.data_ptr(), n_crops,
-                                       crop_map.data_ptr() if crop_map is not None else None, sep.data_ptr(), ret.data_ptr(),
-                                       out.data_ptr(), out.shape[0], M, D, dt,
+        _capi.check(lib.tp_hd_assemble(spec.plan, spec.n_images, feats.data_ptr(), spec.n_crops,
+                                       spec.crop_map.data_ptr() if spec.crop_map is not None else None, sep.data_ptr(),
+                                       ret.data_ptr(), out.data_ptr(), out.shape[0], spec.M, spec.D, spec.dt,
                                        torch.cuda.current_stream(feats.device).cuda_stream),
                     "tp_hd_assemble")
-    return [out[a:a + n] for a, n in spans]
+
+
+def _assemble_backward(spec: _AssembleSpec, dout: torch.Tensor, n_token_crops: int):
+    """-> (dtokens [n_token_crops, M, D], dsep [D], dret [D]) from one tp_hd_assemble_backward call."""
+    lib = _capi.load_library()
+    dev, M, D = dout.device, spec.M, spec.D
+    dtok = torch.empty(n_token_crops, M, D, dtype=dout.dtype, device=dev)
+    dsep = torch.empty(D, dtype=dout.dtype, device=dev)
+    dret = torch.empty(D, dtype=dout.dtype, device=dev)
+    ws = torch.empty(lib.tp_hd_assemble_backward_workspace_bytes(spec.n_images, n_token_crops, D), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _capi.check(lib.tp_hd_assemble_backward(spec.plan, spec.n_images, dout.data_ptr(), dout.shape[0], spec.n_crops,
+                                                spec.crop_map.data_ptr() if spec.crop_map is not None else None,
+                                                dtok.data_ptr(), n_token_crops, dsep.data_ptr(), dret.data_ptr(), M, D, spec.dt,
+                                                ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream),
+                    "tp_hd_assemble_backward")
+    return dtok, dsep, dret
+
+
+class _AssembleFn(torch.autograd.Function):
+    """``out[block rows] = assembled blocks`` as one autograd node (``out`` is modified in place and returned)."""
+
+    @staticmethod
+    def forward(ctx, feats, sep, ret, out, spec):
+        _assemble_launch(spec, feats, sep, ret, out)
+        ctx.spec, ctx.n_token_crops = spec, feats.shape[0]
+        ctx.mark_dirty(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        spec = ctx.spec
+        g = g.contiguous()
+        dfeats = dsep = dret = dprev = None
+        need_f, need_s, need_r, need_o = ctx.needs_input_grad[:4]
+        if need_f or need_s or need_r:
+            dtok, ds, dr = _assemble_backward(spec, g, ctx.n_token_crops)
+            dfeats, dsep, dret = (dtok if need_f else None), (ds if need_s else None), (dr if need_r else None)
+        if need_o:
+            rows = torch.cat([torch.arange(a, a + n) for a, n in spec.spans]).to(g.device)
+            dprev = g.index_fill(0, rows, 0)
+        return dfeats, dsep, dret, dprev, None
 
 
 def splice_layout(input_ids: torch.Tensor, h_block: Sequence[int], w_block: Sequence[int], num_queries: int,
@@ -191,6 +259,11 @@ def splice_layout(input_ids: torch.Tensor, h_block: Sequence[int], w_block: Sequ
     tokens, their flat destination rows (``b * max_len + row``), one ``(dest_row, first_crop, h_block, w_block)`` per image
     token in (sample, position) order, and the number of crop indices consumed (a sample without an image token still
     consumes one, :124-134).  Pure integer logic, no device work."""
+    return _splice_layout(input_ids, h_block, w_block, num_queries, image_token_index)[:5]
+
+
+def _splice_layout(input_ids, h_block, w_block, num_queries, image_token_index):
+    """:func:`splice_layout` plus the per-sample lengths of ``new_input_embeds`` before padding."""
     ids = input_ids.detach().cpu().tolist()
     per_sample, lengths, crop = [], [], 0
     for b, row_ids in enumerate(ids):
@@ -218,7 +291,7 @@ def splice_layout(input_ids: torch.Tensor, h_block: Sequence[int], w_block: Sequ
                 text_dst.append(b * L + seg[1])
             else:
                 img_plan.append((b * L + seg[1], seg[2], seg[3], seg[4]))
-    return L, text_src, text_dst, img_plan, crop
+    return L, text_src, text_dst, img_plan, crop, lengths
 
 
 def build_inputs_embeds(input_ids: torch.Tensor, embed_tokens, image_features: torch.Tensor, h_block: Sequence[int],
@@ -235,17 +308,24 @@ def build_inputs_embeds(input_ids: torch.Tensor, embed_tokens, image_features: t
     same buffer (gaps — the text rows — are left untouched).  ``image_features [n_crops, M, D]`` may be the
     b_max-strided buffer of a ragged all-gather, read through ``crop_map`` (``shard.GatheredTokens``).
     Every image token of sample b uses the grid ``h_block[b] x w_block[b]``; a sample without an image token still
-    consumes one crop index, as in the reference (:124-134).  Labels / attention masks stay host-side list logic
-    (out of scope).  INFERENCE ONLY (see ``assemble_hd_tokens``): raises when a gradient is live on
-    ``image_features`` or on the embedding table."""
+    consumes one crop index, as in the reference (:124-134).  Labels and the attention mask: :func:`build_multimodal_inputs`.
+
+    Differentiable with respect to ``image_features`` and ``embed_tokens`` (see :func:`assemble_hd_tokens`): the text
+    rows and the ',' / '\\n' embeddings (one more ``embed_tokens`` call for ``[sep_id, ret_id]``) reach the table through
+    autograd of those two calls.  The values are the same with and without a live gradient."""
     if not image_features.is_cuda:
         raise RuntimeError("build_inputs_embeds runs only on an AMD GPU (HIP kernel); there is no CPU fallback")
     ids_cpu = input_ids.detach().cpu()
     if ids_cpu.dim() != 2 or len(h_block) != ids_cpu.shape[0] or len(w_block) != ids_cpu.shape[0]:
         raise ValueError("input_ids must be [B, L] with one h_block / w_block entry per sample")
+    layout = _splice_layout(ids_cpu, h_block, w_block, image_features.shape[1], image_token_index)
+    return _embeds_from_layout(input_ids, ids_cpu, layout, embed_tokens, image_features, sep_id, ret_id, crop_map)
+
+
+def _embeds_from_layout(input_ids, ids_cpu, layout, embed_tokens, image_features, sep_id, ret_id, crop_map):
     M, D = image_features.shape[1], image_features.shape[2]
     device, dtype = image_features.device, image_features.dtype
-    L, text_src, text_dst, img_plan, crop = splice_layout(ids_cpu, h_block, w_block, M, image_token_index)
+    L, text_src, text_dst, img_plan, crop = layout[:5]
     n_logical = crop_map.numel() if crop_map is not None else image_features.shape[0]
     if crop != n_logical:
         raise ValueError(f"input_ids / h_block / w_block describe {crop} crops, image_features holds {n_logical}")
@@ -270,3 +350,74 @@ def build_inputs_embeds(input_ids: torch.Tensor, embed_tokens, image_features: t
                 cmap = crop_map.index_select(0, cmap.long()).contiguous()
             assemble_hd_tokens(image_features, hbs, wbs, seps[0], seps[1], out=out, out_rows=rows, crop_map=cmap)
     return out.view(ids_cpu.shape[0], L, D)
+
+
+IGNORE_INDEX = -100           # llava/constants.py
+
+
+def splice_labels_and_mask(input_ids: torch.Tensor, h_block: Sequence[int], w_block: Sequence[int], num_queries: int,
+                           labels: Optional[torch.Tensor] = None, attention_mask: Optional[torch.Tensor] = None,
+                           image_token_index: int = -200, _layout=None):
+    """``(attention_mask, new_labels)`` of ``prepare_inputs_labels_for_multimodal`` in ``mode == 'slice'``
+    (``llava_arch.py:119-231``, default flags) — plain torch on the device of ``labels`` / ``attention_mask`` (CPU too).
+
+    ``new_labels [B, max_len]``: every text token keeps its label, every row of an image block is ``IGNORE_INDEX``
+    (:176), a sample without an image token keeps its labels (:129-130), and shorter samples are padded on the right with
+    ``IGNORE_INDEX`` (:206-212).  ``attention_mask [B, max_len]``: ``True`` for the ``len_b - L`` rows the images added,
+    then the given mask, then ``False`` up to ``max_len`` (:214-221 ragged, :228-230 equal lengths — the same rule).
+    Either output is ``None`` when its input is.  Ragged lengths with an ``attention_mask`` but no ``labels`` raise
+    ``ValueError``: the reference reads an unbound ``_new_labels`` there (:216)."""
+    ids_cpu = input_ids.detach().cpu()
+    B, L_in = ids_cpu.shape
+    layout = _layout if _layout is not None else _splice_layout(ids_cpu, h_block, w_block, num_queries, image_token_index)
+    L, text_src, text_dst, lengths = layout[0], layout[1], layout[2], layout[5]
+    ragged = any(n != lengths[0] for n in lengths)
+    if ragged and attention_mask is not None and labels is None:
+        raise ValueError("ragged lengths with an attention_mask need labels (the reference reads an unbound _new_labels, "
+                         "llava_arch.py:216)")
+    new_labels = new_mask = None
+    if labels is not None:
+        if tuple(labels.shape) != (B, L_in):
+            raise ValueError(f"labels must be [{B}, {L_in}] like input_ids")
+        dev = labels.device
+        new_labels = torch.full((B * L,), IGNORE_INDEX, dtype=labels.dtype, device=dev)
+        if text_src:
+            new_labels[torch.tensor(text_dst, dtype=torch.long, device=dev)] = \
+                labels.reshape(-1).index_select(0, torch.tensor(text_src, dtype=torch.long, device=dev))
+        new_labels = new_labels.view(B, L)
+    if attention_mask is not None:
+        if tuple(attention_mask.shape) != (B, L_in):
+            raise ValueError(f"attention_mask must be [{B}, {L_in}] like input_ids")
+        dev = attention_mask.device
+        left = torch.tensor([n - L_in for n in lengths], dtype=torch.long, device=dev)
+        src = torch.arange(L, device=dev).unsqueeze(0) - left.unsqueeze(1)                 # [B, L] position in the given mask
+        inside = (src >= 0) & (src < L_in)
+        given = attention_mask.gather(1, src.clamp(0, max(L_in - 1, 0))) if L_in > 0 else attention_mask.new_zeros(B, L)
+        new_mask = torch.where(inside, given, (src < 0).to(attention_mask.dtype))
+    return new_mask, new_labels
+
+
+def build_multimodal_inputs(input_ids: torch.Tensor, embed_tokens, image_features: torch.Tensor, h_block: Sequence[int],
+                            w_block: Sequence[int], sep_id: int, ret_id: int, labels: Optional[torch.Tensor] = None,
+                            attention_mask: Optional[torch.Tensor] = None, image_token_index: int = -200,
+                            crop_map: Optional[torch.Tensor] = None):
+    """``(attention_mask, inputs_embeds, labels)``: elements 1, 3 and 4 of what the reference's
+    ``prepare_inputs_labels_for_multimodal`` returns in ``mode == 'slice'`` (``llava_arch.py:100-233``) — the slice
+    branch of a TokenPacker-HD training step (``scripts/v1_5/{pretrain,finetune}_hd.sh``) between the projector and the LLM.
+
+    ``inputs_embeds`` is :func:`build_inputs_embeds` (differentiable with respect to ``image_features`` and
+    ``embed_tokens``); labels and mask come from :func:`splice_labels_and_mask`.  The layout is computed once.
+
+    Out of scope: the ``tune_mm_mlp_adapter and mm_use_im_start_end`` branch that detaches the text embeddings
+    (:161-165, :178-185; both HD scripts set ``mm_use_im_start_end False``), and the decode-step early return (:104-107)
+    — call this only for a prompt with images."""
+    if not image_features.is_cuda:
+        raise RuntimeError("build_multimodal_inputs runs only on an AMD GPU (HIP kernel); there is no CPU fallback")
+    ids_cpu = input_ids.detach().cpu()
+    if ids_cpu.dim() != 2 or len(h_block) != ids_cpu.shape[0] or len(w_block) != ids_cpu.shape[0]:
+        raise ValueError("input_ids must be [B, L] with one h_block / w_block entry per sample")
+    layout = _splice_layout(ids_cpu, h_block, w_block, image_features.shape[1], image_token_index)
+    mask, new_labels = splice_labels_and_mask(ids_cpu, h_block, w_block, image_features.shape[1], labels, attention_mask,
+                                              image_token_index, _layout=layout)
+    embeds = _embeds_from_layout(input_ids, ids_cpu, layout, embed_tokens, image_features, sep_id, ret_id, crop_map)
+    return mask, embeds, new_labels
