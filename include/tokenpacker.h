@@ -267,8 +267,10 @@ enum {
     TP_LINEAR_LN_FOLD = 2,
     TP_LINEAR_ROW_STATS = 4,
     TP_LINEAR_OUT_F32 = 8,     /* retired: use tp_linear_args.out_dtype = TP_F32                    */
-    TP_LINEAR_SAVE_PRE = 16,   /* with GELU: also store the pre-activation (training forward)       */
-    TP_LINEAR_GELU_BWD = 32,   /* multiply the result by gelu'(z), z = fp16 pre-activations (backward) */
+    /* The next two belong to the TRAINING entry points (tp_forward_train* / tp_backward*), which own the pre-activation buffer both
+     * need; tp_linear_args has no field for it and tp_linear() refuses either flag with TP_ERR_INVALID_ARG before anything is enqueued. */
+    TP_LINEAR_SAVE_PRE = 16,   /* with GELU: also store the pre-activation (training forward; not through tp_linear)       */
+    TP_LINEAR_GELU_BWD = 32,   /* multiply the result by gelu'(z), z = fp16 pre-activations (backward; not through tp_linear) */
     TP_LINEAR_NO_STORE = 64    /* with ROW_STATS: compute the row statistics of the (unrounded) result and store NOTHING else
                                   — C may be NULL (the LayerNorm statistics of a tensor nobody needs to materialise)     */
 };

@@ -27,6 +27,68 @@ int tp_test_gemm_route(int M, int N, int K, int flags, int groups);
 size_t tp_test_pack_qr_scratch_bytes(void);
 int tp_test_pack_qr(const void* w2_f16, const float* b2, void* r_f16, float* c_tilde, float* wbar, void* scratch, void* stream);
 
+/* ---- test hooks: the BACKWARD's kernels one at a time (tests/test_gpu_bwd_kernels.py compares each with fp64 math on the same
+ * rounded operands, tests/bwd_ref.py).  Each is a pass-through to the launcher tp_backward itself calls (csrc/tp_internal.h:
+ * bw_*_launch, point_queries_bwd_launch, gemm_launch): same objects, same kernels.  Every hook checks on the HOST what its launcher
+ * leaves to its caller — NULL pointers, 16-byte alignment, element counts / strides that must be multiples of 8 or 4, scratch
+ * sizes — and returns TP_ERR_INVALID_ARG (tp_last_error() says why) before anything is enqueued; otherwise the launcher's status.
+ * All pointers are device pointers unless stated; dtypes are TP_BF16 / TP_F16 (/ TP_F32 where stated); sizes in elements. */
+
+/* dst[c][r] = cast(f(src[r][c])), r < R; exact zeros for R <= r < Rpad; dst is [C][ldd], ldd >= Rpad.  f = identity, or with
+ * `mean_rstd` (fp32 [R][2]) the LayerNorm (v - mean_r) rstd_r gamma_c + beta_c (gamma / beta fp32 [C]).  Source row r lives at
+ * src + (r / rows_per_batch) batch_stride + (r % rows_per_batch) ld (rows_per_batch <= 0 or >= R: contiguous rows, ld apart).
+ * colsum_part (optional, `colsum_floats` floats available, >= ceil(Rpad / 64) * C): [ceil(Rpad / 64)][C] column sums of the SOURCE
+ * values of each 64-row block, the last partial block included.  C, ld, ldd, Rpad, batch_stride: multiples of 8. */
+int tp_test_bw_transpose(int src_dtype, int dst_dtype, const void* src, int64_t ld, int rows_per_batch, int64_t batch_stride,
+                         int R, int C, void* dst, int64_t ldd, int Rpad, const float* mean_rstd, const float* gamma,
+                         const float* beta, float* colsum_part, size_t colsum_floats, void* stream);
+/* `count` (1 .. 8) plain transposes dst_i [C_i][Rpad_i] = cast(src_i [R_i][C_i], rows ld_i apart) in ONE launch.  The six arrays
+ * are HOST arrays of `count` entries. */
+int tp_test_bw_transpose_batch(int src_dtype, int dst_dtype, int count, const void* const* src, const int64_t* ld, const int* R,
+                               const int* C, void* const* dst, const int* Rpad, void* stream);
+/* part[slice][c] = sum over the slice's rows of src[r][c] (fp32; src [R][ld], C % 8 == 0) — RETURNS the number of slices written
+ * (>= 1; a fixed function of R and C), or a negative status.  `part_floats` >= min(512, max(1, R / 64)) * C.  amax_part (optional,
+ * `amax_floats` >= 4096): max |v| per workgroup, NaN sticks; *amax_count (HOST int) = the number of entries written. */
+int tp_test_bw_colsum_rows(int dtype, const void* src, int64_t ld, int64_t R, int C, float* part, size_t part_floats,
+                           float* amax_part, size_t amax_floats, int* amax_count, void* stream);
+/* out[i] = cast(out_scale[0] * sum_k part[k * part_stride + i]), i < n, k in part order; out dtype TP_BF16 / TP_F16 / TP_F32;
+ * out_scale optional (device fp32). */
+int tp_test_bw_reduce_parts(int dst_dtype, const float* part, int64_t part_stride, int nparts, int64_t n, void* out,
+                            const float* out_scale, void* stream);
+/* The same sum in two stages (up to 32 slices of parts, then the slices): n and part_stride multiples of 4, `scratch_floats` >=
+ * 32 * n; n_out (-1: n) = the number of leading columns written. */
+int tp_test_bw_reduce_many_parts(int dst_dtype, const float* part, int64_t part_stride, int nparts, int n, void* out, float* scratch,
+                                 size_t scratch_floats, const float* out_scale, int n_out, void* stream);
+/* scale[0] = S = 2^k with max(amax_part) * S in [16, 32), |k| <= 60; S = 1 for a maximum of 0 / inf / NaN; scale[1] = 1 / S. */
+int tp_test_bw_dynamic_scale(const float* amax_part, int nparts, float* scale, void* stream);
+/* dst_f16[i] = saturate(src[i] * scale[0]), n % 8 == 0; sat_flag (optional device int32): 1 (bit 0) is ORed in when some
+ * |src[i] * scale[0]| >= 65520 or is NaN. */
+int tp_test_bw_scale_cast(int src_dtype, const void* src, int64_t n, const float* scale, void* dst_f16, int* sat_flag, void* stream);
+/* LayerNorm backward over `rows` rows of 1024 on `nblocks` workgroups (four rows each per sweep): dx (gdtype) from dy (gdtype),
+ * x (fp16), mean_rstd (fp32 [rows][2]) and gamma (fp32 [1024]); part [nblocks][3][1024] (`part_floats` >= nblocks * 3072) = every
+ * workgroup's partial sums of dgamma, dbeta and the column sums of the ROUNDED dx — every workgroup writes its slab, also one
+ * without rows.  xn (optional, needs beta) = the LayerNorm's output in gdtype.  sat_flag (optional): 2 (bit 1 of
+ * tp_backward's status word) is ORed in when an fp16 dx reaches 65520 and is clamped. */
+int tp_test_bw_ln_backward(int gdtype, const void* dy, const void* x_f16, const float* mean_rstd, const float* gamma, void* dx,
+                           float* part, size_t part_floats, int nblocks, int64_t rows, const float* beta, void* xn, int* sat_flag,
+                           void* stream);
+/* Region-attention backward: q [B M, 1024], k / v [B grid^2, 1024] fp16; dout, dq [B M, 1024], dk, dv [B grid^2, 1024] gdtype.
+ * mask_mode 0: the unmasked launch (mask, dmask NULL).  1 / 2: the additive fp32 mask ([s*s] | [(M B) 8, s*s]) enters the
+ * recomputed logits; dmask (optional, fp32, the mask's layout) = dL/dmask times inv_scale[0] (optional).  A mode-1 dmask needs
+ * part (`part_bytes` >= B M ceil4(s*s) * 4) and redscratch (`redscratch_floats` >= 32 * ceil4(s*s)).  sat_flag: 4 (bit 2)
+ * when an fp16 dq / dk clamps. */
+int tp_test_bw_region_attention(int gdtype, const void* q, const void* k, const void* v, const void* dout, void* dq, void* dk,
+                                void* dv, int B, int grid, int s, const float* mask, int mask_mode, float* dmask,
+                                const float* inv_scale, float* part, size_t part_bytes, float* redscratch, size_t redscratch_floats,
+                                int* sat_flag, void* stream);
+/* dx [B, grid^2, 1024] (dtype, contiguous) = downsample^T(dq0 fp32 [B (grid/s)^2, 1024]) * inv_scale[0] (optional). */
+int tp_test_point_queries_bwd(int dtype, const float* dq0, const float* inv_scale, void* dx, int B, int grid, int s, void* stream);
+/* C [M, ldc] = cast(out_scale[0] * (A [M, lda] · W [N, K]^T) * gelu'(Z [M, ldz])) — the data-gradient GEMM of tp_backward with its
+ * training epilogue: flags 0 or TP_LINEAR_GELU_BWD (then Z, fp16, is required), out_scale optional, tile 0 (auto) / 128 / 256.
+ * N % 128 == 0, K % 64 == 0; the training epilogue exists for 16-bit outputs only (TP_F32 with Z or out_scale: TP_ERR_INVALID_ARG). */
+int tp_test_linear_bwd(int M, int N, int K, int dtype, int out_dtype, int flags, const void* A, int64_t lda, const void* W, void* C,
+                       int64_t ldc, const void* Z, int64_t ldz, const float* out_scale, int tile, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -306,3 +306,95 @@ def test_gemm_routing_policy_is_host_logic_and_pinned():
         assert r(147456, 2048, 4096, G) == T192 and r(147456, 1024, 1024, S | NS, 2) != T192
     finally:
         set_tuning(_capi.TP_TUNE_GEMM_TILE, 0)
+
+
+def test_tp_linear_refuses_the_training_flags():
+    """TP_LINEAR_SAVE_PRE / TP_LINEAR_GELU_BWD need a pre-activation buffer tp_linear_args has no field for: tp_linear refuses
+    them on the host (a launch would address that buffer from NULL).  The message is asserted as well as the status."""
+    lib = _capi.load_library()
+    fake = 4096                                                      # non-NULL, 16-byte aligned; never dereferenced on a refusal
+    for flag, name in ((_capi.TP_LINEAR_SAVE_PRE, "TP_LINEAR_SAVE_PRE"), (_capi.TP_LINEAR_GELU_BWD, "TP_LINEAR_GELU_BWD")):
+        for extra in (0, _capi.TP_LINEAR_GELU):
+            a = _capi.tp_linear_args()
+            a.M, a.N, a.K, a.dtype, a.out_dtype = 256, 256, 64, _capi.TP_F16, _capi.TP_F16
+            a.lda, a.ldc, a.A, a.W, a.C, a.bias = 64, 256, fake, fake, fake, fake
+            a.flags = flag | extra
+            assert lib.tp_linear(ctypes.byref(a), None) == _capi.TP_ERR_INVALID_ARG
+            msg = lib.tp_last_error().decode()
+            assert name in msg and "training entry points" in msg, msg
+
+
+def test_backward_kernel_hooks_refuse_bad_arguments():
+    """Every tp_test_bw_* / tp_test_point_queries_bwd / tp_test_linear_bwd hook turns a mistaken call — NULL, misaligned, a count
+    that is not a multiple of 8 / 4, a scratch too small — into TP_ERR_INVALID_ARG on the host (include/tokenpacker_test.h)."""
+    tl = _capi.load_test_library()
+    E = _capi.TP_ERR_INVALID_ARG
+    F16, BF16, F32 = _capi.TP_F16, _capi.TP_BF16, _capi.TP_F32
+    p, odd = 4096, 4104                                               # fake device pointers: aligned | 8 bytes off; never dereferenced
+    big = 1 << 30
+
+    def refused(fn, good, bad_variants):
+        for i, val in bad_variants:
+            args = list(good)
+            args[i] = val
+            assert fn(*args) == E, (fn.__name__, i, val)
+            msg = tl.tp_last_error().decode()                         # (the hook's own refusal, or its launcher's host-side one)
+            assert msg.startswith((fn.__name__, "bw ", "tp gemm")), msg
+
+    # (src_dtype, dst_dtype, src, ld, rows_per_batch, batch_stride, R, C, dst, ldd, Rpad, mean_rstd, gamma, beta, colsum_part, colsum_floats, stream)
+    refused(tl.tp_test_bw_transpose, [F16, BF16, p, 64, 0, 0, 100, 64, p, 104, 104, None, None, None, None, 0, None],
+            [(2, None), (8, None), (2, odd), (8, odd), (0, F32), (1, 7), (3, 60), (3, 56), (7, 60), (9, 100), (10, 100), (10, 96), (6, 0),
+             (11, p), (14, p), (4, 50)])
+    refused(tl.tp_test_bw_transpose, [F16, F16, p, 64, 50, 3200, 100, 64, p, 104, 104, None, None, None, p, 2 * 64, None],
+            [(5, 3196), (5, 1600), (15, 2 * 64 - 1)])
+    arr = lambda t, v: (t * len(v))(*v)                               # noqa: E731
+    vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
+    good = [F16, F16, 2, arr(vp, [p, p]), arr(i64, [64, 64]), arr(i32, [10, 10]), arr(i32, [64, 64]), arr(vp, [p, p]), arr(i32, [16, 16]), None]
+    refused(tl.tp_test_bw_transpose_batch, good,
+            [(2, 0), (2, 9), (0, F32), (3, None), (7, None), (3, arr(vp, [p, None])), (3, arr(vp, [p, odd])), (8, arr(i32, [16, 8])),
+             (8, arr(i32, [16, 12])), (4, arr(i64, [64, 60])), (6, arr(i32, [64, 60]))])
+    cnt = ctypes.c_int(0)
+    # (dtype, src, ld, R, C, part, part_floats, amax_part, amax_floats, amax_count, stream)
+    refused(tl.tp_test_bw_colsum_rows, [BF16, p, 1024, 4096, 1024, p, 64 * 1024, p, 4096, ctypes.byref(cnt), None],
+            [(1, None), (5, None), (1, odd), (0, F32), (2, 1020), (2, 512), (4, 1020), (3, 0), (6, 64 * 1024 - 1), (8, 4095), (9, None)])
+    # (dst_dtype, part, part_stride, nparts, n, out, out_scale, stream)
+    refused(tl.tp_test_bw_reduce_parts, [F32, p, 1024, 4, 1024, p, None, None],
+            [(1, None), (5, None), (1, odd), (5, odd), (0, 9), (3, 0), (4, 0), (2, 1000)])
+    # (dst_dtype, part, part_stride, nparts, n, out, scratch, scratch_floats, out_scale, n_out, stream)
+    refused(tl.tp_test_bw_reduce_many_parts, [BF16, p, 1024, 300, 1024, p, p, 32 * 1024, None, -1, None],
+            [(1, None), (5, None), (6, None), (1, odd), (6, odd), (0, 5), (3, 0), (4, 1022), (2, 1022), (2, 1020), (7, 32 * 1024 - 1), (9, 1025),
+             (9, -2)])
+    refused(tl.tp_test_bw_dynamic_scale, [p, 8, p, None], [(0, None), (2, None), (1, 0)])
+    # (src_dtype, src, n, scale, dst_f16, sat_flag, stream)
+    refused(tl.tp_test_bw_scale_cast, [BF16, p, 1024, p, p, None, None], [(1, None), (3, None), (4, None), (0, F32), (2, 0)])
+    for i, val in ((2, 1020), (1, odd), (4, odd)):                    # (the launcher's own checks)
+        args = [BF16, p, 1024, p, p, None, None]
+        args[i] = val
+        assert tl.tp_test_bw_scale_cast(*args) == E
+    # (gdtype, dy, x, mean_rstd, gamma, dx, part, part_floats, nblocks, rows, beta, xn, sat_flag, stream)
+    refused(tl.tp_test_bw_ln_backward, [F16, p, p, p, p, p, p, 7 * 3072, 7, 100, None, None, None, None],
+            [(1, None), (2, None), (3, None), (4, None), (5, None), (6, None), (1, odd), (2, odd), (5, odd), (0, F32), (7, 7 * 3072 - 1),
+             (8, 0), (8, 70000), (9, 0), (11, odd)])
+    args = [F16, p, p, p, p, p, p, 7 * 3072, 7, 100, None, p, None, None]     # xn without beta: the launcher's check
+    assert tl.tp_test_bw_ln_backward(*args) == E
+    # (gdtype, q, k, v, dout, dq, dk, dv, B, grid, s, mask, mask_mode, dmask, inv_scale, part, part_bytes, redscratch, redscratch_floats, sat_flag, stream)
+    good = [BF16, p, p, p, p, p, p, p, 2, 24, 3, None, 0, None, None, None, 0, None, 0, None, None]
+    refused(tl.tp_test_bw_region_attention, good,
+            [(i, None) for i in range(1, 8)] + [(i, odd) for i in range(1, 8)] + [(0, F32), (8, 0), (10, 5), (10, 0), (12, 3), (11, p), (13, p),
+                                                                                 (12, 1), (12, 2)])
+    good = [BF16, p, p, p, p, p, p, p, 2, 24, 3, p, 1, p, None, p, 2 * 64 * 12 * 4, p, 32 * 12, None, None]
+    refused(tl.tp_test_bw_region_attention, good, [(15, None), (17, None), (15, odd), (13, odd), (16, 2 * 64 * 12 * 4 - 1), (18, 32 * 12 - 1)])
+    # (dtype, dq0, inv_scale, dx, B, grid, s, stream)
+    refused(tl.tp_test_point_queries_bwd, [F16, p, None, p, 1, 24, 2, None], [(1, None), (3, None), (1, odd), (3, odd), (0, F32), (4, 0), (6, 5), (6, 0)])
+    # (M, N, K, dtype, out_dtype, flags, A, lda, W, C, ldc, Z, ldz, out_scale, tile, stream)
+    good = [256, 256, 64, F16, F16, _capi.TP_LINEAR_GELU_BWD, p, 64, p, p, 256, p, 512, None, 128, None]
+    refused(tl.tp_test_linear_bwd, good,
+            [(6, None), (8, None), (9, None), (11, None), (6, odd), (9, odd), (11, odd), (3, F32), (4, 9), (5, _capi.TP_LINEAR_GELU), (5, 16),
+             (7, 60), (7, 56), (10, 250), (10, 128), (12, 250), (12, 128), (14, 64), (0, 0)])
+    assert tl.tp_test_linear_bwd(256, 256, 64, F16, F16, 0, p, 64, p, p, 256, p, 256, None, 0, None) == E        # Z without the flag
+    assert tl.tp_test_linear_bwd(256, 200, 64, F16, F16, 0, p, 64, p, p, 256, None, 0, None, 0, None) == E       # (gemm_launch: N % 128)
+    # the training epilogue exists for 16-bit outputs only: refused on the host by the GEMM launchers, on either tile
+    for tile in (128, 256):
+        assert tl.tp_test_linear_bwd(256, 256, 128, F16, F32, _capi.TP_LINEAR_GELU_BWD, p, 128, p, p, 256, p, 256, None, tile, None) == E
+        assert "16-bit output" in tl.tp_last_error().decode()
+        assert tl.tp_test_linear_bwd(256, 256, 128, F16, F32, 0, p, 128, p, p, 256, None, 0, p, tile, None) == E

@@ -15,6 +15,7 @@ TP_ABI_VERSION = 6
 TP_BF16, TP_F16, TP_F32 = 0, 1, 2
 TP_OK, TP_ERR_INVALID_ARG, TP_ERR_BAD_SCALE, TP_ERR_WORKSPACE, TP_ERR_LAUNCH = 0, -1, -2, -3, -4
 TP_LINEAR_GELU, TP_LINEAR_LN_FOLD, TP_LINEAR_ROW_STATS = 1, 2, 4
+TP_LINEAR_SAVE_PRE, TP_LINEAR_GELU_BWD = 16, 32        # the training entry points' flags: tp_linear refuses them
 TP_LINEAR_NO_STORE = 64
 TP_TUNE_GEMM_TILE, TP_TUNE_XCD_SWIZZLE, TP_TUNE_FOLD_OUT_PROJ, TP_TUNE_DYNAMIC_TILES, TP_TUNE_Q_SIDE_STREAM = 0, 1, 2, 3, 4
 TP_TUNE_RESERVE_CUS, TP_TUNE_ABSORB_KV, TP_TUNE_FUSE_KV_LN, TP_TUNE_LN_MERGE, TP_TUNE_FUSE_ATTN = 5, 6, 7, 8, 9
@@ -63,7 +64,11 @@ EXPORTED_SYMBOLS = (
     "tp_tuning_create", "tp_tuning_destroy", "tp_tuning_set", "tp_tuning_get", "tp_gather_alloc_flags", "tp_gather_free_flags", "tp_gather_export", "tp_gather_open", "tp_gather_close", "tp_gather_push", "tp_gather_sync",
 )
 # include/tokenpacker_test.h: the stateless test hooks — libtokenpacker_exp.so only (load_test_library()), never the product library
-TEST_SYMBOLS = ("tp_test_occupy_cus", "tp_test_pair_occupancy", "tp_test_gemm_route", "tp_test_pack_qr", "tp_test_pack_qr_scratch_bytes")
+TEST_SYMBOLS = ("tp_test_occupy_cus", "tp_test_pair_occupancy", "tp_test_gemm_route", "tp_test_pack_qr", "tp_test_pack_qr_scratch_bytes",
+                # the backward's kernels one at a time (tests/test_gpu_bwd_kernels.py)
+                "tp_test_bw_transpose", "tp_test_bw_transpose_batch", "tp_test_bw_colsum_rows", "tp_test_bw_reduce_parts",
+                "tp_test_bw_reduce_many_parts", "tp_test_bw_dynamic_scale", "tp_test_bw_scale_cast", "tp_test_bw_ln_backward",
+                "tp_test_bw_region_attention", "tp_test_point_queries_bwd", "tp_test_linear_bwd")
 TP_COUNTER_SIDE_STREAMS, TP_COUNTER_PAIR_LAUNCHES = 0, 1
 EXP_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtokenpacker_exp.so")
 
@@ -297,6 +302,24 @@ def load_test_library(path: str = EXP_LIB_PATH) -> ctypes.CDLL:
     lib.tp_test_pack_qr_scratch_bytes.argtypes = []
     lib.tp_test_pack_qr.restype = c_int
     lib.tp_test_pack_qr.argtypes = [c_void_p] * 7
+    # the backward's kernels (include/tokenpacker_test.h); v = a device (or NULL) pointer
+    v = c_void_p
+    for name, argtypes in (
+            ("tp_test_bw_transpose", [c_int, c_int, v, c_int64, c_int, c_int64, c_int, c_int, v, c_int64, c_int, v, v, v, v, c_size_t, v]),
+            ("tp_test_bw_transpose_batch", [c_int, c_int, c_int, POINTER(c_void_p), POINTER(c_int64), POINTER(c_int), POINTER(c_int),
+                                            POINTER(c_void_p), POINTER(c_int), v]),
+            ("tp_test_bw_colsum_rows", [c_int, v, c_int64, c_int64, c_int, v, c_size_t, v, c_size_t, POINTER(c_int), v]),
+            ("tp_test_bw_reduce_parts", [c_int, v, c_int64, c_int, c_int64, v, v, v]),
+            ("tp_test_bw_reduce_many_parts", [c_int, v, c_int64, c_int, c_int, v, v, c_size_t, v, c_int, v]),
+            ("tp_test_bw_dynamic_scale", [v, c_int, v, v]),
+            ("tp_test_bw_scale_cast", [c_int, v, c_int64, v, v, v, v]),
+            ("tp_test_bw_ln_backward", [c_int, v, v, v, v, v, v, c_size_t, c_int, c_int64, v, v, v, v]),
+            ("tp_test_bw_region_attention", [c_int, v, v, v, v, v, v, v, c_int, c_int, c_int, v, c_int, v, v, v, c_size_t, v, c_size_t, v, v]),
+            ("tp_test_point_queries_bwd", [c_int, v, v, v, c_int, c_int, c_int, v]),
+            ("tp_test_linear_bwd", [c_int, c_int, c_int, c_int, c_int, c_int, v, c_int64, v, v, c_int64, v, c_int64, v, c_int, v])):
+        fn = getattr(lib, name)
+        fn.restype = c_int
+        fn.argtypes = argtypes
     lib.tp_set_tuning.restype = c_int
     lib.tp_set_tuning.argtypes = [c_int, c_int]
     lib.tp_version.restype = c_int

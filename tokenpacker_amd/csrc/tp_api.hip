@@ -664,6 +664,12 @@ int tp_linear_stats_parts(const tp_linear_args* a) {
 
 int tp_linear(const tp_linear_args* a, void* stream) {
     if (!a || !a->A || !a->W || (!a->C && !(a->flags & TP_LINEAR_NO_STORE))) { set_error("tp_linear: NULL argument"); return TP_ERR_INVALID_ARG; }
+    // (tp_linear_args has no field for the pre-activation buffer either flag needs: the epilogue would address it from NULL)
+    if (a->flags & (TP_LINEAR_SAVE_PRE | TP_LINEAR_GELU_BWD)) {
+        set_error("tp_linear: %s belongs to the training entry points (tp_forward_train / tp_backward own the pre-activation buffer); "
+                  "tp_linear cannot serve it", (a->flags & TP_LINEAR_SAVE_PRE) ? "TP_LINEAR_SAVE_PRE" : "TP_LINEAR_GELU_BWD");
+        return TP_ERR_INVALID_ARG;
+    }
     if ((a->flags & TP_LINEAR_NO_STORE) && !(a->flags & TP_LINEAR_ROW_STATS)) {
         set_error("tp_linear: TP_LINEAR_NO_STORE only makes sense with TP_LINEAR_ROW_STATS");
         return TP_ERR_INVALID_ARG;
