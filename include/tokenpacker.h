@@ -459,6 +459,68 @@ int tp_hd_assemble_backward(const tp_hd_image* plan, int n_images, const void* d
                             const int32_t* crop_map, void* dtokens, int64_t n_token_crops, void* dsep, void* dret, int M, int D,
                             int dtype, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- token splice: text and visual tokens into inputs_embeds, labels and attention_mask (one launch) -------------------
+ * What `prepare_inputs_labels_for_multimodal` (llava_arch.py:100-233) builds with a Python walk per sample, in any mode:
+ * ONE gather writes every row of out [batch * out_len, D] exactly once, plus out_labels and out_mask [batch, out_len].
+ * The caller describes each output row by one int32 code, kind << 30 | payload:
+ *   TP_SPLICE_TEXT     payload = flat position b * in_len + pos: the row is table[ids_dev[position]] (the id is read on the
+ *                      device), its label is labels[position];
+ *   TP_SPLICE_LITERAL  payload = a table row (the ',' and '\n' rows of mode 'slice'); label -100;
+ *   TP_SPLICE_FEATURE  payload = k * M + m: token m of logical feature block k of feats [n_feat_blocks, M, D] — block
+ *                      crop_map[k] with a `crop_map` (device int32 [n_logical], as in tp_hd_assemble); label -100;
+ *   TP_SPLICE_PAD      a zero row; label -100.
+ * The plan is batch * out_len codes followed by one int32 per sample, its length before padding; `plan_host` is read by the
+ * call's validation, `plan_dev` is the caller's device copy of the same words.  out_mask[b, r] is 1 for r < len_b - in_len
+ * (the rows the images added), then mask[b, r - (len_b - in_len)], then 0 (llava_arch.py:214-221, :228-230); `mask_bytes`
+ * is 1 (bool) or 8 (int64).  labels / out_labels (int64) and mask / out_mask may be NULL in pairs.  `ids_host` (the ids as
+ * the host knows them, or NULL) lets the validation refuse an id outside [0, V); the kernel never forms an address from
+ * an id or a crop_map value outside its buffer (such a row is written as zeros).
+ *
+ * tp_splice_backward is the transpose, from dout [batch * out_len, D], with the same struct and plan:
+ *   dfeats [n_feat_blocks, M, D] (NULL = not wanted), the WHOLE buffer: a feature row that an output row reads gets that
+ *     dout row (a copy); every other row is zero (the block an image-less sample consumes, unmapped crop_map slots).  A
+ *     feature row read twice is refused.  Needs `workspace` of tp_splice_backward_workspace_bytes(n_feat_blocks, M) =
+ *     n_feat_blocks * M * 4 bytes rounded up to 256.
+ *   dtable [V, D] (NULL = not wanted: nothing is launched for it), dense like nn.Embedding's gradient: row t is the sum
+ *     of the dout rows whose source is table row t (TEXT and LITERAL alike), accumulated in fp32 in increasing row order
+ *     and rounded once — no atomics, two runs give the same bits; a row read once is a copy, a row never read and the
+ *     `padding_idx` row (-1: none) are zero.  The caller sorts: order_host / order_dev hold n_table_rows int32 output rows
+ *     (those that read the table), stably sorted by table row, followed by V + 1 int32 offsets (table row t's readers are
+ *     order[offsets[t] .. offsets[t + 1])); needs ids_host.
+ * Both entries validate on the host first (TP_ERR_INVALID_ARG: NULL or misaligned pointers, D % 8, dtype, a code outside
+ * its buffer, counts that do not match the plan), then only enqueue: no allocation, no synchronisation.  The plan belongs
+ * to one batch, so a call cannot be replayed from a captured graph for another. */
+enum { TP_SPLICE_TEXT = 0, TP_SPLICE_LITERAL = 1, TP_SPLICE_FEATURE = 2, TP_SPLICE_PAD = 3 };
+typedef struct tp_splice_args {
+    int32_t batch, in_len, out_len, M, D, dtype;
+    int64_t V, n_feat_blocks, n_logical;      /* n_logical: crop_map's length; n_feat_blocks without a crop_map */
+    const int32_t* plan_host;                 /* codes [batch * out_len] | lengths [batch] */
+    const int32_t* plan_dev;
+    const int64_t* ids_host;                  /* [batch * in_len], or NULL (forward) */
+    const int64_t* ids_dev;
+    const void* table;                        /* [V, D] */
+    const void* feats;                        /* [n_feat_blocks, M, D] */
+    const int32_t* crop_map;
+    const int64_t* labels;
+    const void* mask;
+    int32_t mask_bytes, reserved;
+    void* out;
+    int64_t* out_labels;
+    void* out_mask;
+    /* backward only */
+    const void* dout;
+    void* dfeats;
+    void* dtable;
+    int64_t padding_idx, n_table_rows;
+    const int32_t* order_host;                /* order [n_table_rows] | offsets [V + 1] */
+    const int32_t* order_dev;
+    void* workspace;
+    size_t workspace_bytes;
+} tp_splice_args;
+int tp_splice(const tp_splice_args* args, void* stream);
+size_t tp_splice_backward_workspace_bytes(int64_t n_feat_blocks, int M);
+int tp_splice_backward(const tp_splice_args* args, void* stream);
+
 /* ---- TokenPacker-HD image slicing (the step before the CLIP tower) ---------------------------------------------
  * Replaces the resize / zero-pad / tile code of the data loader and the eval drivers (llava/train/train.py:695-731):
  * image [3, H, W] fp32 (already normalised) -> crops [h_block*w_block (+1), 3, block, block] fp32: the image resized

@@ -6,6 +6,8 @@ runs (``tokenpacker_amd.shard``).  Importing this package needs neither a GPU no
 library; *using* the projector needs both.
 """
 from .projector import TokenPacker, build_vision_projector  # noqa: F401
+from . import splice  # noqa: F401
+from .splice import build_multimodal_inputs, splice_layout  # noqa: F401
 
-__all__ = ["TokenPacker", "build_vision_projector"]
+__all__ = ["TokenPacker", "build_vision_projector", "splice", "build_multimodal_inputs", "splice_layout"]
 __version__ = "0.1.0"

@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = (
     "tp_backward_inputs_workspace_bytes", "tp_backward_inputs", "tp_backward_inputs_parts",
     "tp_forward_train_masked", "tp_forward_parts_masked", "tp_backward_masked",
     "tp_hd_assemble_backward_workspace_bytes", "tp_hd_assemble_backward",
+    "tp_splice", "tp_splice_backward_workspace_bytes", "tp_splice_backward",
     "tp_tuning_create", "tp_tuning_destroy", "tp_tuning_set", "tp_tuning_get", "tp_gather_alloc_flags", "tp_gather_free_flags", "tp_gather_export", "tp_gather_open", "tp_gather_close", "tp_gather_push", "tp_gather_sync",
 )
 # include/tokenpacker_test.h: the stateless test hooks — libtokenpacker_exp.so only (load_test_library()), never the product library
@@ -126,6 +127,22 @@ class tp_linear_args(Structure):
 class tp_hd_image(Structure):
     _fields_ = [("first_crop", c_int32), ("h_block", c_int32), ("w_block", c_int32), ("reserved", c_int32),
                 ("out_row", c_int64)]
+
+
+TP_SPLICE_TEXT, TP_SPLICE_LITERAL, TP_SPLICE_FEATURE, TP_SPLICE_PAD = 0, 1, 2, 3
+
+
+class tp_splice_args(Structure):
+    """tp_splice / tp_splice_backward (include/tokenpacker.h, "token splice"): one struct for both directions."""
+    _fields_ = [("batch", c_int32), ("in_len", c_int32), ("out_len", c_int32), ("M", c_int32), ("D", c_int32), ("dtype", c_int32),
+                ("V", c_int64), ("n_feat_blocks", c_int64), ("n_logical", c_int64),
+                ("plan_host", c_void_p), ("plan_dev", c_void_p), ("ids_host", c_void_p), ("ids_dev", c_void_p),
+                ("table", c_void_p), ("feats", c_void_p), ("crop_map", c_void_p), ("labels", c_void_p), ("mask", c_void_p),
+                ("mask_bytes", c_int32), ("reserved", c_int32),
+                ("out", c_void_p), ("out_labels", c_void_p), ("out_mask", c_void_p),
+                ("dout", c_void_p), ("dfeats", c_void_p), ("dtable", c_void_p),
+                ("padding_idx", c_int64), ("n_table_rows", c_int64),
+                ("order_host", c_void_p), ("order_dev", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t)]
 
 
 _lib = None
@@ -269,6 +286,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.tp_hd_assemble_backward.restype = c_int
     lib.tp_hd_assemble_backward.argtypes = [POINTER(tp_hd_image), c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64,
                                             c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]
+    lib.tp_splice.restype = c_int
+    lib.tp_splice.argtypes = [POINTER(tp_splice_args), c_void_p]
+    lib.tp_splice_backward_workspace_bytes.restype = c_size_t
+    lib.tp_splice_backward_workspace_bytes.argtypes = [c_int64, c_int]
+    lib.tp_splice_backward.restype = c_int
+    lib.tp_splice_backward.argtypes = [POINTER(tp_splice_args), c_void_p]
 
     if lib.tp_version() != TP_ABI_VERSION:
         raise TokenPackerLibraryError(
