@@ -1,7 +1,7 @@
 /* tokenpacker_test.h — test hooks and probe builds of the TokenPacker HIP library.  NOT part of the product ABI
  * (include/tokenpacker.h): these entry points exist only in libtokenpacker_exp.so (`make -C tokenpacker_amd/csrc exp`, built by
- * __graft_entry__.build() beside the product library from the same sources + csrc/tp_test_hooks.hip, the GEMM kernels' timing-probe
- * instantiations (-DTP_BUILD_PROBES: TP_TUNE_PAIR_DEBUG) and csrc/experimental/).  All of them are stateless: a test may call them
+ * __graft_entry__.build() beside the product library from the same sources + csrc/tp_test_hooks.hip and the GEMM kernels' timing-probe
+ * instantiations (-DTP_BUILD_PROBES: TP_TUNE_PAIR_DEBUG)).  All of them are stateless: a test may call them
  * in libtokenpacker_exp.so while the module under test runs on libtokenpacker_hip.so. */
 #ifndef TOKENPACKER_TEST_H
 #define TOKENPACKER_TEST_H

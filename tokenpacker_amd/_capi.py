@@ -305,7 +305,7 @@ _test_lib = None
 
 def load_test_library(path: str = EXP_LIB_PATH) -> ctypes.CDLL:
     """dlopen ``libtokenpacker_exp.so`` (include/tokenpacker_test.h: the stateless test hooks, the GEMM kernels' timing-probe
-    instantiations, csrc/experimental/) beside the product library.  The two libraries share no state: use this one for the
+    instantiations) beside the product library.  The two libraries share no state: use this one for the
     ``tp_test_*`` hooks only (or, for the probe tools, as the whole library: ``TP_LIB_VARIANT=exp``)."""
     global _test_lib
     if _test_lib is not None:
