@@ -27,6 +27,13 @@ int tp_test_gemm_route(int M, int N, int K, int flags, int groups);
 size_t tp_test_pack_qr_scratch_bytes(void);
 int tp_test_pack_qr(const void* w2_f16, const float* b2, void* r_f16, float* c_tilde, float* wbar, void* scratch, void* stream);
 
+/* ---- test hook (host logic only, no GPU needed): where tp_pack_weights puts one tensor of the packed image.  `name` is a field of
+ * PackedLayout (csrc/tp_internal.h: "w_kv0" .. "status", in the order of their offsets; "total": the image's size, 0 bytes);
+ * *offset = its byte offset in the image, *bytes = the size the layout reserved for it before the 256-byte alignment.  An unknown
+ * name or a hidden_size that is not a positive multiple of 128: TP_ERR_INVALID_ARG (tp_last_error() says why).
+ * tests/test_gpu_pack_image.py slices the image with it. */
+int tp_test_packed_layout(int hidden_size, const char* name, size_t* offset, size_t* bytes);
+
 /* ---- test hooks: the BACKWARD's kernels one at a time (tests/test_gpu_bwd_kernels.py compares each with fp64 math on the same
  * rounded operands, tests/bwd_ref.py).  Each is a pass-through to the launcher tp_backward itself calls (csrc/tp_internal.h:
  * bw_*_launch, point_queries_bwd_launch, gemm_launch): same objects, same kernels.  Every hook checks on the HOST what its launcher

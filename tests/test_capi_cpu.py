@@ -398,3 +398,45 @@ def test_backward_kernel_hooks_refuse_bad_arguments():
         assert tl.tp_test_linear_bwd(256, 256, 128, F16, F32, _capi.TP_LINEAR_GELU_BWD, p, 128, p, p, 256, p, 256, None, tile, None) == E
         assert "16-bit output" in tl.tp_last_error().decode()
         assert tl.tp_test_linear_bwd(256, 256, 128, F16, F32, 0, p, 128, p, p, 256, None, 0, p, tile, None) == E
+
+
+def _packed_layout_fields():
+    """The fields of PackedLayout, in declaration order, from csrc/tp_internal.h itself."""
+    src = open(os.path.join(ROOT, "tokenpacker_amd", "csrc", "tp_internal.h")).read()
+    body = re.search(r"struct PackedLayout \{(.*?)\n\};", src, flags=re.S).group(1)
+    body = re.sub(r"//[^\n]*", "", body)
+    return [n.strip() for decl in re.findall(r"size_t ([^;]+);", body) for n in decl.split(",")]
+
+
+@pytest.mark.parametrize("hidden", [384, 4096])
+def test_packed_layout_hook(hidden):
+    """tp_test_packed_layout (include/tokenpacker_test.h, host logic only): every PackedLayout field resolves; offsets are 256-byte
+    aligned and strictly increasing in declaration order; the reserved ranges do not overlap; `status` and `total` are what the
+    product ABI reports; a bad name or width is refused."""
+    from tests import pack_ref
+    lib, tl = _capi.load_library(), _capi.load_test_library()
+    fields = _packed_layout_fields()
+    assert fields[0] == "w_kv0" and fields[-2:] == ["status", "total"] and len(fields) == len(set(fields)) == 38
+    assert fields[:-1] == list(pack_ref.field_specs(hidden))                 # the tests' own table names the same fields in the same order
+    d = _capi.make_desc(1, 24, 2, hidden, _capi.TP_BF16)
+    off, nbytes = ctypes.c_size_t(), ctypes.c_size_t()
+    lay = []
+    for name in fields:
+        assert tl.tp_test_packed_layout(hidden, name.encode(), ctypes.byref(off), ctypes.byref(nbytes)) == _capi.TP_OK, name
+        lay.append((name, off.value, nbytes.value))
+    assert lay[0][1] == 0
+    for (name, o, n), (_, nxt, _) in zip(lay[:-1], lay[1:]):
+        assert o % 256 == 0 and n > 0, name
+        assert o < nxt and o + n <= nxt, f"{name} [{o}, {o + n}) runs into the next field at {nxt}"
+        assert nxt - (o + n) < 256, name                                     # (nothing but alignment padding in between)
+    by_name = {name: (o, n) for name, o, n in lay}
+    assert by_name["status"] == (lib.tp_packed_status_offset(ctypes.byref(d)), 256)
+    assert by_name["total"] == (lib.tp_packed_weight_bytes(ctypes.byref(d)), 0)
+    assert by_name["w_m2"][1] == hidden * hidden * 2 and by_name["w_cc_v3"][1] == 2 * 1024 * 1024 * 2
+    E = _capi.TP_ERR_INVALID_ARG
+    assert tl.tp_test_packed_layout(hidden, b"w_kv1", ctypes.byref(off), ctypes.byref(nbytes)) == E
+    assert "w_kv1" in tl.tp_last_error().decode()
+    assert tl.tp_test_packed_layout(hidden + 64, b"w_kv0", ctypes.byref(off), ctypes.byref(nbytes)) == E
+    assert "multiple of 128" in tl.tp_last_error().decode()
+    assert tl.tp_test_packed_layout(0, b"w_kv0", ctypes.byref(off), ctypes.byref(nbytes)) == E
+    assert tl.tp_test_packed_layout(hidden, None, ctypes.byref(off), ctypes.byref(nbytes)) == E

@@ -66,6 +66,7 @@ EXPORTED_SYMBOLS = (
 )
 # include/tokenpacker_test.h: the stateless test hooks — libtokenpacker_exp.so only (load_test_library()), never the product library
 TEST_SYMBOLS = ("tp_test_occupy_cus", "tp_test_pair_occupancy", "tp_test_gemm_route", "tp_test_pack_qr", "tp_test_pack_qr_scratch_bytes",
+                "tp_test_packed_layout",     # where the pack puts each tensor of the image (tests/test_gpu_pack_image.py)
                 # the backward's kernels one at a time (tests/test_gpu_bwd_kernels.py)
                 "tp_test_bw_transpose", "tp_test_bw_transpose_batch", "tp_test_bw_colsum_rows", "tp_test_bw_reduce_parts",
                 "tp_test_bw_reduce_many_parts", "tp_test_bw_dynamic_scale", "tp_test_bw_scale_cast", "tp_test_bw_ln_backward",
@@ -325,6 +326,8 @@ def load_test_library(path: str = EXP_LIB_PATH) -> ctypes.CDLL:
     lib.tp_test_pack_qr_scratch_bytes.argtypes = []
     lib.tp_test_pack_qr.restype = c_int
     lib.tp_test_pack_qr.argtypes = [c_void_p] * 7
+    lib.tp_test_packed_layout.restype = c_int
+    lib.tp_test_packed_layout.argtypes = [c_int, c_char_p, POINTER(c_size_t), POINTER(c_size_t)]
     # the backward's kernels (include/tokenpacker_test.h); v = a device (or NULL) pointer
     v = c_void_p
     for name, argtypes in (

@@ -60,33 +60,35 @@ TuningScope::~TuningScope() { tls_tuning = (const tp_tuning*)prev_; }
 
 static inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
-PackedLayout packed_layout(int D) {
+PackedLayout packed_layout(int D, PackedLayout* reserved) {
     PackedLayout L{};
     size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes); return o; };
+    // (`reserved`, optional: the byte count each field asked for, before the alignment — what tp_test_packed_layout reports)
+    auto take = [&](size_t PackedLayout::* f, size_t bytes) { L.*f = off; if (reserved) reserved->*f = bytes; off = align_up(off + bytes); };
     const size_t E = kEmbed;
-    L.w_kv0 = take(2 * E * kMulti * 2);  L.b_kv0 = take(2 * E * 4);
-    L.w_kv2 = take(2 * E * E * 2);       L.b_kv2 = take(2 * E * 4);
-    L.w_q1 = take(E * E * 2);
-    L.w_in_kv = take(2 * E * E * 2);     L.c_in_kv = take(2 * E * 4);  L.b_in_kv = take(2 * E * 4);
-    L.w_in_q = take(E * E * 2);          L.c_in_q = take(E * 4);       L.b_in_q = take(E * 4);
-    L.w_qt = take(E * E * 2);
-    L.w_qt_c = take(E * E * 2);
-    L.w_c_kv = take(2 * E * E * 2);      L.d_in_kv = take(2 * E * 4);
-    L.w_c_q = take(E * E * 2);
-    L.w_cc_kv = take(2 * E * E * 2);     L.d_cc_kv = take(2 * E * 4);
-    L.w_cc_q = take(E * E * 2);          L.w_qt_cc = take(E * E * 2);
-    L.w_cc_v3 = take(2 * E * E * 2);
-    L.w_r_kv = take(2 * E * E * 2);      L.c_r_kv = take(2 * E * 4);
-    L.w_r_q = take(E * E * 2);
-    L.wbar = take(3 * (E + 1) * 4);      L.scratch_qr = take(pack_qr_scratch_bytes(3));
-    L.w_out = take(E * E * 2);           L.b_out = take(E * 4);
-    L.w_m0 = take((size_t)D * E * 2);    L.b_m0 = take((size_t)D * 4);
-    L.w_m2 = take((size_t)D * D * 2);    L.b_m2 = take((size_t)D * 4);
-    L.w_om = take((size_t)D * E * 2);    L.b_om = take((size_t)D * 4);
-    L.scratch_t = take(E * E * 2);       L.scratch_p = take((size_t)(D > (int)E ? D : (int)E) * E * 4);   // fp32 [max(D, E), E]
-    L.status = take(256);
+    take(&PackedLayout::w_kv0, 2 * E * kMulti * 2);  take(&PackedLayout::b_kv0, 2 * E * 4);
+    take(&PackedLayout::w_kv2, 2 * E * E * 2);       take(&PackedLayout::b_kv2, 2 * E * 4);
+    take(&PackedLayout::w_q1, E * E * 2);
+    take(&PackedLayout::w_in_kv, 2 * E * E * 2);     take(&PackedLayout::c_in_kv, 2 * E * 4);  take(&PackedLayout::b_in_kv, 2 * E * 4);
+    take(&PackedLayout::w_in_q, E * E * 2);          take(&PackedLayout::c_in_q, E * 4);       take(&PackedLayout::b_in_q, E * 4);
+    take(&PackedLayout::w_qt, E * E * 2);
+    take(&PackedLayout::w_qt_c, E * E * 2);
+    take(&PackedLayout::w_c_kv, 2 * E * E * 2);      take(&PackedLayout::d_in_kv, 2 * E * 4);
+    take(&PackedLayout::w_c_q, E * E * 2);
+    take(&PackedLayout::w_cc_kv, 2 * E * E * 2);     take(&PackedLayout::d_cc_kv, 2 * E * 4);
+    take(&PackedLayout::w_cc_q, E * E * 2);          take(&PackedLayout::w_qt_cc, E * E * 2);
+    take(&PackedLayout::w_cc_v3, 2 * E * E * 2);
+    take(&PackedLayout::w_r_kv, 2 * E * E * 2);      take(&PackedLayout::c_r_kv, 2 * E * 4);
+    take(&PackedLayout::w_r_q, E * E * 2);
+    take(&PackedLayout::wbar, 3 * (E + 1) * 4);      take(&PackedLayout::scratch_qr, pack_qr_scratch_bytes(3));
+    take(&PackedLayout::w_out, E * E * 2);           take(&PackedLayout::b_out, E * 4);
+    take(&PackedLayout::w_m0, (size_t)D * E * 2);    take(&PackedLayout::b_m0, (size_t)D * 4);
+    take(&PackedLayout::w_m2, (size_t)D * D * 2);    take(&PackedLayout::b_m2, (size_t)D * 4);
+    take(&PackedLayout::w_om, (size_t)D * E * 2);    take(&PackedLayout::b_om, (size_t)D * 4);
+    take(&PackedLayout::scratch_t, E * E * 2);       take(&PackedLayout::scratch_p, (size_t)(D > (int)E ? D : (int)E) * E * 4);   // fp32 [max(D, E), E]
+    take(&PackedLayout::status, 256);
     L.total = off;
+    if (reserved) reserved->total = 0;
     return L;
 }
 

@@ -277,12 +277,15 @@ int pack_ln_fold_launch(int dtype, const void* w, const void* bias, const void* 
 int count_saturated_launch(const void* buf, long long n, int* count, hipStream_t stream);
 
 // ---- packed-weight and workspace layouts (tp_api.hip) -----------------------------------------
+// (the fields are declared in the order of their offsets: tp_test_packed_layout and tests/test_capi_cpu.py rely on it)
 struct PackedLayout {
     size_t w_kv0, b_kv0;          // [2048,4096] io dtype (consumed with the raw inputs), [2048] f32
     size_t w_kv2, b_kv2;          // [2][1024,1024] f16, [2][1024] f32
     size_t w_q1;                  // [1024,1024] f16
     size_t w_in_kv, c_in_kv, b_in_kv;   // LN-folded in-proj for k, v: [2][1024,1024] f16, [2][1024] f32 x2
     size_t w_in_q, c_in_q, b_in_q;      // LN-folded in-proj for q
+    size_t w_qt;                  // [8][1024][128] f16: per-head transposes of the LN-folded K in-proj (absorbed schedule)
+    size_t w_qt_c;                // the same of Wc_k (absorbed schedule on the fused LayerNorm chain: the kernel walks Hkv)
     size_t w_c_kv, d_in_kv;       // fused LayerNorm chain: Wc = W'·W2 [2][1024,1024] f16, d = W'·b2 [2][1024] f32
     size_t w_c_q;                 // the same for the query side: W'q·Wq1 [1024,1024] f16 (q_proj_1 has no bias: d = 0)
     // triangular statistics (TP_TUNE_TRI_STATS, tp_pack_qr.hip): the chain with the mean folded away — Wc' = W'·W2c, d' = W'·b2c
@@ -298,8 +301,6 @@ struct PackedLayout {
     size_t w_r_q;                 // [1024,1024] f16
     size_t wbar;                  // pack scratch: [3][1025] f32 column means of W2 (k, v, q) and the mean of b2 behind each
     size_t scratch_qr;            // pack scratch: three fp64 [1024][1025] matrices + Householder vectors
-    size_t w_qt;                  // [8][1024][128] f16: per-head transposes of the LN-folded K in-proj (absorbed schedule)
-    size_t w_qt_c;                // the same of Wc_k (absorbed schedule on the fused LayerNorm chain: the kernel walks Hkv)
     size_t w_out, b_out;          // [1024,1024] f16, [1024] f32
     size_t w_m0, b_m0;            // [D,1024] f16, [D] f32
     size_t w_m2, b_m2;            // [D,D] f16, [D] f32
@@ -309,7 +310,7 @@ struct PackedLayout {
                                   // [1] = 1 when w_om / b_om were built (TP_TUNE_FOLD_OUT_PROJ at pack time)
     size_t total;
 };
-PackedLayout packed_layout(int D);
+PackedLayout packed_layout(int D, PackedLayout* reserved = nullptr);   // reserved (optional): each field's byte count before alignment
 
 // The schedule tp_forward runs for a descriptor under the tuning table OF THE MOMENT (tp_api.hip plan_schedule): one place
 // decides; forward_impl, the workspace layout and the debug scan read it.  `masked`: the forward carries an attn_mask.

@@ -2,6 +2,7 @@
 // the product library does not export them.  Stateless: each reads nothing but its arguments and the device.
 #include "tp_internal.h"
 #include "../../include/tokenpacker_test.h"
+#include <string.h>
 
 using namespace tp;
 #define TP_TRY(expr) do { int rc_ = (expr); if (rc_ != TP_OK) return rc_; } while (0)
@@ -36,6 +37,30 @@ int tp_test_pack_qr(const void* w2_f16, const float* b2, void* r_f16, float* c_t
     TP_TRY(pack_qr_center_launch(w2_f16, b2, scratch, 0, wbar, st));
     TP_TRY(pack_qr_factor_launch(scratch, 1, st));
     return pack_qr_extract_launch(scratch, 0, r_f16, c_tilde, st, nullptr);
+}
+
+// Where tp_pack_weights puts a tensor of the image (host logic only): `name` is a PackedLayout field (tp_internal.h), "total" included.
+int tp_test_packed_layout(int hidden_size, const char* name, size_t* offset, size_t* bytes) {
+    TP_REQUIRE(name && offset && bytes, "tp_test_packed_layout: NULL argument");
+    TP_REQUIRE(hidden_size > 0 && hidden_size % 128 == 0, "tp_test_packed_layout: hidden_size %d is not a positive multiple of 128", hidden_size);
+    struct Field { const char* name; size_t PackedLayout::* member; };
+#define TP_FIELD(f) {#f, &PackedLayout::f}
+    static const Field fields[] = {                                   // in declaration order
+        TP_FIELD(w_kv0), TP_FIELD(b_kv0), TP_FIELD(w_kv2), TP_FIELD(b_kv2), TP_FIELD(w_q1),
+        TP_FIELD(w_in_kv), TP_FIELD(c_in_kv), TP_FIELD(b_in_kv), TP_FIELD(w_in_q), TP_FIELD(c_in_q), TP_FIELD(b_in_q),
+        TP_FIELD(w_qt), TP_FIELD(w_qt_c), TP_FIELD(w_c_kv), TP_FIELD(d_in_kv), TP_FIELD(w_c_q),
+        TP_FIELD(w_cc_kv), TP_FIELD(d_cc_kv), TP_FIELD(w_cc_q), TP_FIELD(w_qt_cc), TP_FIELD(w_cc_v3),
+        TP_FIELD(w_r_kv), TP_FIELD(c_r_kv), TP_FIELD(w_r_q), TP_FIELD(wbar), TP_FIELD(scratch_qr),
+        TP_FIELD(w_out), TP_FIELD(b_out), TP_FIELD(w_m0), TP_FIELD(b_m0), TP_FIELD(w_m2), TP_FIELD(b_m2), TP_FIELD(w_om), TP_FIELD(b_om),
+        TP_FIELD(scratch_t), TP_FIELD(scratch_p), TP_FIELD(status), TP_FIELD(total)};
+#undef TP_FIELD
+    static_assert(sizeof(fields) / sizeof(fields[0]) * sizeof(size_t) == sizeof(PackedLayout), "a PackedLayout field is missing from the table");
+    PackedLayout reserved{};
+    const PackedLayout L = packed_layout(hidden_size, &reserved);
+    for (const Field& f : fields)
+        if (strcmp(name, f.name) == 0) { *offset = L.*(f.member); *bytes = reserved.*(f.member); return TP_OK; }
+    set_error("tp_test_packed_layout: no PackedLayout field named '%s'", name);
+    return TP_ERR_INVALID_ARG;
 }
 
 // ---- the backward's kernels, one launcher each (tp_internal.h: bw_*_launch, point_queries_bwd_launch, gemm_launch) -------------
