@@ -37,6 +37,8 @@ extern "C" {
  * gradients with respect to x / x_multi).  Every ABI 5 entry point, struct and workspace size is unchanged, and so are its results. */
 /* ABI 6, extended (detected by symbol; the version stays 6): tp_attn_mask, tp_forward_train_masked, tp_forward_parts_masked and
  * tp_backward_masked (training with an attn_mask, and its gradient).  Nothing else changes. */
+/* ABI 6, extended again (by symbol, the version stays 6): tp_grad_sink, tp_backward_sink and tp_backward_plan (a backward that skips
+ * the gradients of frozen parameters and can accumulate into fp32 buffers).  Every older entry point keeps its behaviour and its bits. */
 #define TP_ABI_VERSION 6
 
 typedef enum tp_status {
@@ -405,6 +407,60 @@ int tp_backward_masked(const tp_desc* desc, const void* x_multi, const void* con
                        const tp_weights* raw, const void* packed_weights, const void* train_workspace, const void* dy,
                        const tp_grads* grads, const tp_input_grads* ig, const tp_attn_mask* mask, void* bw_workspace,
                        size_t bw_workspace_bytes, void* stream);
+
+/* ABI 6 extension (a binding detects it by symbol): the backward into a GRADIENT SINK.  tp_backward* computes all 23 parameter
+ * gradients in the model dtype and overwrites their destination; a partially frozen projector (LoRA-style runs that freeze the K/V
+ * branches — 4 x the rows of the query side, a first-layer weight gradient that contracts over K = 4096) pays for gradients nobody
+ * reads, and micro-batch accumulation rounds twice per micro-step (bf16 .grad += bf16 g).  The sink says, per parameter, whether its
+ * gradient is wanted, and lets every wanted one leave as fp32 — optionally ADDED to what the buffer holds (the fp32 `main_grad`
+ * of Megatron / Apex / Transformer Engine).
+ *   grads       one pointer per parameter (tp_grads); NULL = not wanted: nothing is computed for it alone, nothing is written
+ *   dtype       element type of every non-NULL entry: desc.dtype, or TP_F32 (then every entry 16-byte aligned).  An fp32 entry is
+ *               the fp32 sum the model-dtype gradient is rounded from (times the fp16 chain's exact 1 / S): rounding it to desc.dtype
+ *               gives tp_backward's value bit for bit; nothing is clamped
+ *   accumulate  0: overwrite; 1 (TP_F32 only): out += gradient — one plain load, add and store per element in a fixed order, no
+ *               atomics: deterministic
+ * tp_backward_sink takes tp_backward_masked's arguments with `sink` in place of `grads`; `sink`, `ig` and `mask` are each nullable
+ * (mask NULL = no mask), and at least one output must be asked for: a non-NULL sink entry, an input gradient or mask->grad.
+ * Workspace: tp_backward_workspace_bytes, or tp_backward_inputs_workspace_bytes when `ig` is given.  The status word keeps its
+ * meaning.  TP_ERR_INVALID_ARG, before anything is enqueued: accumulate with a dtype other than TP_F32 (or a value other than 0 / 1),
+ * a dtype that is neither desc.dtype nor TP_F32, a misaligned fp32 entry, nothing asked for.  With every entry non-NULL, dtype =
+ * desc.dtype and accumulate = 0 the call IS tp_backward / _inputs / _masked: the same launches in the same order, the same bits.
+ * Every wanted gradient of a partial sink has the bits the full backward gives it.
+ *
+ * tp_backward_plan: which stages a backward runs for what is wanted — pure host logic, no device; tp_backward_sink decides its
+ * launches with this same function.  Bit i of `wanted_params` is field i of tp_grads (q_proj_1_weight = bit 0 .. mlp_2_bias =
+ * bit 22); the result is an OR of TP_BWD_STAGE_*.  A stage runs if and only if something wanted lies at or below it in the chain
+ * (dy -> mlp[2] -> mlp[0] -> out_proj -> attention -> the q | k | v chains -> the K/V layers):
+ *   DY          the pass over dy (column sums, max |dy| and scale, the fp16 copy): always (a model-dtype chain that does not want
+ *               mlp.2.bias has nothing to take from it and launches nothing); MLP2_BIAS: the reduction into mlp.2.bias
+ *   MLP2_WGRAD, MLP0_BIAS, MLP0_WGRAD, OUT_BIAS, OUT_WGRAD    that parameter alone
+ *   DZ2, DA1, DO   the dgrads dy -> dZ2 -> dA1 -> dO: anything below the layer, or that layer's own parameters for the dgrad in front
+ *   ATTENTION   in_proj_*, any ln_*, q_proj_1, any k_proj_1.* / v_proj_1.*, dx, dx_multi, dmask
+ *   Q_CHAIN     dgrad dQ -> dq1 and the LayerNorm-q backward: ln_q_1.*, in_proj_weight (its q third reads the LayerNorm output that
+ *               backward writes), q_proj_1.weight, dx
+ *   K_CHAIN / V_CHAIN   the same for a K/V branch: its ln_*, *_proj_1.2.* (the bias is the column sum of the LayerNorm backward's dx),
+ *               *_proj_1.0.*, in_proj_weight, dx_multi
+ *   DZ1         the dgrads dH2 -> dZ1: any k_proj_1.0.* / v_proj_1.0.*, or dx_multi (each half where its chain ran)
+ *   KV0_WGRAD   the first K/V layer's column sums and its ONE joint contraction: any of its four parameters; a member that is not
+ *               wanted has its reduction skipped
+ * in_proj_weight / in_proj_bias are single tensors: wanting one means all three of its thirds (the bias thirds are column sums of
+ * dQ, dK and dO: they need the attention backward, not the chains). */
+enum { TP_BWD_STAGE_DY = 1 << 0, TP_BWD_STAGE_MLP2_BIAS = 1 << 1, TP_BWD_STAGE_MLP2_WGRAD = 1 << 2, TP_BWD_STAGE_DZ2 = 1 << 3,
+       TP_BWD_STAGE_MLP0_BIAS = 1 << 4, TP_BWD_STAGE_MLP0_WGRAD = 1 << 5, TP_BWD_STAGE_DA1 = 1 << 6,
+       TP_BWD_STAGE_OUT_BIAS = 1 << 7, TP_BWD_STAGE_OUT_WGRAD = 1 << 8, TP_BWD_STAGE_DO = 1 << 9, TP_BWD_STAGE_ATTENTION = 1 << 10,
+       TP_BWD_STAGE_Q_CHAIN = 1 << 11, TP_BWD_STAGE_K_CHAIN = 1 << 12, TP_BWD_STAGE_V_CHAIN = 1 << 13, TP_BWD_STAGE_DZ1 = 1 << 14,
+       TP_BWD_STAGE_KV0_WGRAD = 1 << 15, TP_BWD_STAGE_ALL = (1 << 16) - 1 };
+typedef struct tp_grad_sink {
+    tp_grads grads;      /* NULL entry = this parameter's gradient is not wanted                  */
+    int32_t  dtype;      /* element type of every non-NULL entry: desc.dtype or TP_F32            */
+    int32_t  accumulate; /* 0: overwrite; 1: out += gradient (TP_F32 only)                        */
+} tp_grad_sink;
+int tp_backward_sink(const tp_desc* desc, const void* x_multi, const void* const xm_parts[4], const int64_t xm_strides[3],
+                     const tp_weights* raw, const void* packed_weights, const void* train_workspace, const void* dy,
+                     const tp_grad_sink* sink, const tp_input_grads* ig, const tp_attn_mask* mask, void* bw_workspace,
+                     size_t bw_workspace_bytes, void* stream);
+uint32_t tp_backward_plan(uint32_t wanted_params, int want_dx, int want_dx_multi, int want_dmask);
 
 /* The backward's weight-gradient contraction on its own (what autograd computes for every nn.Linear of
  * builder.py:59-83):  dw[n_out, k_in] = sum over the `rows` token rows of dy[r, n] * x[r, k], read from the ROW-MAJOR

@@ -60,6 +60,7 @@ EXPORTED_SYMBOLS = (
     "tp_get_tuning", "tp_release_stream",
     "tp_backward_inputs_workspace_bytes", "tp_backward_inputs", "tp_backward_inputs_parts",
     "tp_forward_train_masked", "tp_forward_parts_masked", "tp_backward_masked",
+    "tp_backward_sink", "tp_backward_plan",
     "tp_hd_assemble_backward_workspace_bytes", "tp_hd_assemble_backward",
     "tp_splice", "tp_splice_backward_workspace_bytes", "tp_splice_backward",
     "tp_tuning_create", "tp_tuning_destroy", "tp_tuning_set", "tp_tuning_get", "tp_gather_alloc_flags", "tp_gather_free_flags", "tp_gather_export", "tp_gather_open", "tp_gather_close", "tp_gather_push", "tp_gather_sync",
@@ -114,6 +115,20 @@ class tp_attn_mask(Structure):
     """The attn_mask of tp_forward_train_masked's step for tp_backward_masked: the fp32 additive mask, its mode (1: [s*s], 2:
     [(M*B)*8, s*s]) and where dL/dmask goes (NULL = not wanted)."""
     _fields_ = [("mask", c_void_p), ("mode", c_int32), ("reserved", c_int32), ("grad", c_void_p)]
+
+
+class tp_grad_sink(Structure):
+    """Where tp_backward_sink puts the parameter gradients: one pointer per parameter (NULL = not wanted, nothing is computed for it
+    alone), the element type of the non-NULL entries (the model dtype or TP_F32) and whether they accumulate (TP_F32 only)."""
+    _fields_ = [("grads", tp_grads), ("dtype", c_int32), ("accumulate", c_int32)]
+
+
+# tp_backward_plan's result: which stages a backward runs for what is wanted (include/tokenpacker.h)
+BWD_STAGE_NAMES = ("DY", "MLP2_BIAS", "MLP2_WGRAD", "DZ2", "MLP0_BIAS", "MLP0_WGRAD", "DA1", "OUT_BIAS", "OUT_WGRAD", "DO",
+                   "ATTENTION", "Q_CHAIN", "K_CHAIN", "V_CHAIN", "DZ1", "KV0_WGRAD")
+for _i, _n in enumerate(BWD_STAGE_NAMES):
+    globals()["TP_BWD_STAGE_" + _n] = 1 << _i
+TP_BWD_STAGE_ALL = (1 << len(BWD_STAGE_NAMES)) - 1
 
 
 class tp_linear_args(Structure):
@@ -270,6 +285,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.tp_backward_masked.argtypes = [POINTER(tp_desc), c_void_p, POINTER(c_void_p), POINTER(c_int64), POINTER(tp_weights),
                                        c_void_p, c_void_p, c_void_p, POINTER(tp_grads), POINTER(tp_input_grads),
                                        POINTER(tp_attn_mask), c_void_p, c_size_t, c_void_p]
+    lib.tp_backward_sink.restype = c_int
+    lib.tp_backward_sink.argtypes = [POINTER(tp_desc), c_void_p, POINTER(c_void_p), POINTER(c_int64), POINTER(tp_weights),
+                                     c_void_p, c_void_p, c_void_p, POINTER(tp_grad_sink), POINTER(tp_input_grads),
+                                     POINTER(tp_attn_mask), c_void_p, c_size_t, c_void_p]
+    lib.tp_backward_plan.restype = c_uint32
+    lib.tp_backward_plan.argtypes = [c_uint32, c_int, c_int, c_int]
     lib.tp_wgrad_workspace_bytes.restype = c_size_t
     lib.tp_wgrad_workspace_bytes.argtypes = [c_int, c_int]
     lib.tp_wgrad.restype = c_int
@@ -426,6 +447,15 @@ class TuningContext:
             pass
 
 
+def backward_plan(wanted=(), want_dx: bool = False, want_dx_multi: bool = False, want_dmask: bool = False):
+    """Names of the stages (``BWD_STAGE_NAMES``) a backward runs when the parameters named in ``wanted`` (state-dict names, or a
+    bit mask in ``WEIGHT_FIELDS`` order) and the given input / mask gradients are wanted: ``tp_backward_plan``, the function the
+    library itself decides its launches with.  Host logic only, no device."""
+    bits = wanted if isinstance(wanted, int) else sum(1 << WEIGHT_FIELDS.index(n) for n in wanted)
+    plan = load_library().tp_backward_plan(bits, int(want_dx), int(want_dx_multi), int(want_dmask))
+    return tuple(n for i, n in enumerate(BWD_STAGE_NAMES) if plan >> i & 1)
+
+
 def strides3(st) -> "ctypes.Array":
     return (c_int64 * 3)(int(st[0]), int(st[1]), int(st[2]))
 
@@ -452,5 +482,5 @@ def get_tuning(key: int) -> int:
 
 
 __all__ = [n for n in dir() if n.startswith(("TP_", "tp_"))] + [
-    "load_library", "load_test_library", "last_error", "check", "make_desc", "strides3", "set_tuning", "get_tuning", "TuningContext",
+    "load_library", "load_test_library", "last_error", "check", "make_desc", "strides3", "backward_plan", "BWD_STAGE_NAMES", "set_tuning", "get_tuning", "TuningContext",
     "TokenPackerLibraryError", "WEIGHT_FIELDS", "EXPORTED_SYMBOLS", "TEST_SYMBOLS", "LIB_PATH", "EXP_LIB_PATH", "byref"]

@@ -194,6 +194,19 @@ reduce_parts_kernel(const float* __restrict__ part, long long part_stride, int n
     if (out_scale) s *= out_scale[0];                   // (a power of two: exact)
     out[i] = sat_cast<TD>(s);
 }
+// The accumulate variant of an fp32 gradient sink (tp_backward_sink, accumulate = 1): out[i] = out[i] + s * scale — a plain load and
+// store per element in the same fixed order (no atomics: a second run gives the same bits).  The product and the sum are rounded
+// separately (no fused multiply-add), so the result is torch's `out + g` on the overwrite-mode g, bit for bit.
+__global__ void __launch_bounds__(256)
+reduce_parts_accum_kernel(const float* __restrict__ part, long long part_stride, int nparts, long long n, float* __restrict__ out,
+                          const float* __restrict__ out_scale) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float s = 0.f;
+    for (int k = 0; k < nparts; ++k) s += part[(long long)k * part_stride + i];
+    if (out_scale) s = __fmul_rn(s, out_scale[0]);
+    out[i] = __fadd_rn(out[i], s);
+}
 
 // Same sum, many parts (column-sum / LayerNorm partials: hundreds to thousands of parts of a few thousand values),
 // in two stages so that the whole chip streams the partials with 16-byte loads: stage 1 — grid (n / 256 column
@@ -228,7 +241,7 @@ reduce_cols_stage1_kernel(const float* __restrict__ part, long long part_stride,
 }
 
 int bw_reduce_many_parts_launch(int dst_dtype, const float* part, long long part_stride, int nparts, int n, void* out,
-                                float* scratch, hipStream_t stream, const float* out_scale, int n_out) {
+                                float* scratch, hipStream_t stream, const float* out_scale, int n_out, bool accumulate) {
     if ((n & 3) || (part_stride & 3) || ((uintptr_t)part & 15)) {
         set_error("bw reduce: n / part stride must be multiples of 4 floats, partials 16-byte aligned");
         return TP_ERR_INVALID_ARG;
@@ -238,7 +251,7 @@ int bw_reduce_many_parts_launch(int dst_dtype, const float* part, long long part
     hipLaunchKernelGGL(reduce_cols_stage1_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)S), dim3(256), 0, stream,
                        part, part_stride, nparts, n, scratch);
     if (int rc = check_launch("reduce_cols_stage1_kernel")) return rc;
-    return bw_reduce_parts_launch(dst_dtype, scratch, n, S, n_out < 0 ? n : n_out, out, stream, out_scale);
+    return bw_reduce_parts_launch(dst_dtype, scratch, n, S, n_out < 0 ? n : n_out, out, stream, out_scale, accumulate);
 }
 
 // Column sums of a row-major 16-bit matrix (bias gradients of the layers whose weight gradient reads dY in place):
@@ -330,8 +343,13 @@ int bw_colsum_rows_launch(int dtype, const void* src, long long ld, long long R,
 }
 
 int bw_reduce_parts_launch(int dst_dtype, const float* part, long long part_stride, int nparts, long long n, void* out,
-                           hipStream_t stream, const float* out_scale) {
+                           hipStream_t stream, const float* out_scale, bool accumulate) {
     const unsigned blocks = (unsigned)((n + 255) / 256);
+    if (accumulate) {                                   // (an fp32 gradient sink only: tp_backward_sink refuses anything else)
+        if (dst_dtype != TP_F32) { set_error("bw reduce: accumulation needs an fp32 destination (got dtype %d)", dst_dtype); return TP_ERR_INVALID_ARG; }
+        hipLaunchKernelGGL(reduce_parts_accum_kernel, dim3(blocks), dim3(256), 0, stream, part, part_stride, nparts, n, (float*)out, out_scale);
+        return check_launch("reduce_parts_accum_kernel");
+    }
     if (dst_dtype == TP_BF16)
         hipLaunchKernelGGL(reduce_parts_kernel<bf16_t>, dim3(blocks), dim3(256), 0, stream, part, part_stride, nparts, n, (bf16_t*)out, out_scale);
     else if (dst_dtype == TP_F16)

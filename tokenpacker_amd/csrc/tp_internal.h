@@ -371,7 +371,7 @@ struct TransposeBatch {
 };
 int bw_transpose_batch_launch(int src_dtype, int dst_dtype, const TransposeBatch& tb, hipStream_t stream);
 int bw_reduce_parts_launch(int dst_dtype, const float* part, long long part_stride, int nparts, long long n, void* out,
-                           hipStream_t stream, const float* out_scale = nullptr);
+                           hipStream_t stream, const float* out_scale = nullptr, bool accumulate = false);
 // Dynamic power-of-two scale of a gradient tensor (the backward of a bf16 model runs its chain in fp16 — 11-bit mantissas, the
 // saved fp16 activations read in place by the weight gradients — and fp16's range needs the incoming dy brought to a known
 // magnitude): bw_scale_from_partials_launch turns the per-workgroup max |dy| a column-sum pass left behind into scale[0] = S = 2^k with
@@ -388,14 +388,15 @@ struct WgradX {
     const void* const* parts; int n_part;             // NULL / 0: one tensor
 };
 bool wgrad_tt_supported(long long R, int Nout, int Kin, const WgradX& X, long long ldy);
-// rows [0, split_row) of dW go to grad_out, rows [split_row, Nout) to grad_out_hi (split_row = 0: all to grad_out)
+// rows [0, split_row) of dW go to grad_out, rows [split_row, Nout) to grad_out_hi (split_row = 0: all to grad_out; with a split, a
+// NULL side is not reduced).  `accumulate` (out_dtype TP_F32 only): dW is added to what the output holds (reduce_parts_accum_kernel)
 int wgrad_tt_launch(int dtype, const void* dY, long long ldy, const WgradX& X, long long R, int Nout, int Kin,
                     float* part, size_t part_bytes, int out_dtype, void* grad_out, int* counters, hipStream_t stream,
-                    void* grad_out_hi = nullptr, int split_row = 0, const float* out_scale = nullptr);
+                    void* grad_out_hi = nullptr, int split_row = 0, const float* out_scale = nullptr, bool accumulate = false);
 size_t wgrad_tt_part_bytes(int Nout, int Kin);
 int wgrad_tn_launch(int dtype, const void* dY, long long ldy, const void* XT, long long rpad, long long R, int Nout, int Kin,
                     float* part, size_t part_bytes, int out_dtype, void* grad_out, int* counters, hipStream_t stream,
-                    const float* out_scale = nullptr);
+                    const float* out_scale = nullptr, bool accumulate = false);
 
 constexpr int kColsumMaxSlices = 512;              // row slices of the column-sum kernel: scratch = slices * C floats
 // amax_part / amax_count (optional): the pass also leaves max |v| per workgroup (*amax_count entries, <= kColsumAmaxParts) — the
@@ -407,7 +408,8 @@ int bw_scale_from_partials_launch(const float* amax_part, int nparts, float* sca
 constexpr int kReduceSlices = 32;                  // stage-1 slices of the many-parts reduction: scratch = kReduceSlices * n floats
 // (`n_out` >= 0: write only the first n_out of the n columns — n padded to a multiple of 4 for the stage-1 loads)
 int bw_reduce_many_parts_launch(int dst_dtype, const float* part, long long part_stride, int nparts, int n, void* out,
-                                float* scratch, hipStream_t stream, const float* out_scale = nullptr, int n_out = -1);
+                                float* scratch, hipStream_t stream, const float* out_scale = nullptr, int n_out = -1,
+                                bool accumulate = false);
 // part: [nblocks][3][E] — dgamma, dbeta, colsum(dx) partials.  beta / xn (optional): also write the LayerNorm's output in gdtype
 int bw_ln_backward_launch(int gdtype, const void* dy, const void* x_f16, const float* mean_rstd, const float* gamma,
                           void* dx, float* part, int nblocks, long long rows, hipStream_t stream, const float* beta = nullptr,

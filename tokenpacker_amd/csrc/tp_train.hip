@@ -1,5 +1,5 @@
 // tp_train.hip — training entry points of libtokenpacker_hip.so: the forward that keeps what the backward needs,
-// and the backward pass of the projector (gradients of all 23 parameters).  The CLIP features come from a frozen tower in
+// and the backward pass of the projector (gradients of all 23 parameters, or — tp_backward_sink — of those that are wanted).  The CLIP features come from a frozen tower in
 // the reference's own recipe (llava/train/train.py:950-953, clip_encoder.py:46 `@torch.no_grad()`) and get none from
 // tp_backward; tp_backward_inputs adds them on request (opt-in: a trainable / LoRA-tuned tower, attribution):
 //   x_multi     dx_multi = dZ1 · [Wk0; Wv0] / S                           one dgrad GEMM, rounded once to the model dtype
@@ -144,7 +144,7 @@ bool wgrad_tt_supported(long long R, int Nout, int Kin, const WgradX& X, long lo
 
 int wgrad_tt_launch(int dtype, const void* dY, long long ldy, const WgradX& X, long long R, int Nout, int Kin,
                     float* part, size_t part_bytes, int out_dtype, void* grad_out, int* counters, hipStream_t stream,
-                    void* grad_out_hi, int split_row, const float* out_scale) {
+                    void* grad_out_hi, int split_row, const float* out_scale, bool accumulate) {
     if (!wgrad_tt_supported(R, Nout, Kin, X, ldy)) {
         set_error("tp wgrad: unsupported shape R=%lld Nout=%d Kin=%d (need Kin %% 256 == 0, strides %% 8 == 0, batches of a multiple of 64 rows)",
                   R, Nout, Kin);
@@ -166,18 +166,22 @@ int wgrad_tt_launch(int dtype, const void* dY, long long ldy, const WgradX& X, l
     a.M = Nout; a.N = Kin; a.K = (int)Ks; a.groups = S; a.tt_rows = R; a.rows_per_batch = Nout; a.tile = 256;
     a.tile_counters = S <= 4 ? counters : nullptr;       // (a queue slot holds [4 groups][8 XCDs] heads)
     TP_TRY(gemm_launch(dtype, TP_F32, a, stream));
-    if (!grad_out_hi || split_row <= 0 || split_row >= Nout)
-        return bw_reduce_parts_launch(out_dtype, part, (long long)Nout * Kin, S, (long long)Nout * Kin, grad_out, stream, out_scale);
-    TP_TRY(bw_reduce_parts_launch(out_dtype, part, (long long)Nout * Kin, S, (long long)split_row * Kin, grad_out, stream, out_scale));
-    return bw_reduce_parts_launch(out_dtype, part + (size_t)split_row * Kin, (long long)Nout * Kin, S,
-                                  (long long)(Nout - split_row) * Kin, grad_out_hi, stream, out_scale);
+    if (split_row <= 0 || split_row >= Nout)
+        return bw_reduce_parts_launch(out_dtype, part, (long long)Nout * Kin, S, (long long)Nout * Kin, grad_out, stream, out_scale, accumulate);
+    // (two parameters behind one contraction: a side nobody wants — NULL — is not reduced, and nothing is written through it)
+    if (grad_out)
+        TP_TRY(bw_reduce_parts_launch(out_dtype, part, (long long)Nout * Kin, S, (long long)split_row * Kin, grad_out, stream, out_scale, accumulate));
+    if (grad_out_hi)
+        TP_TRY(bw_reduce_parts_launch(out_dtype, part + (size_t)split_row * Kin, (long long)Nout * Kin, S,
+                                      (long long)(Nout - split_row) * Kin, grad_out_hi, stream, out_scale, accumulate));
+    return TP_OK;
 }
 
 // dW[Nout, Kin] = dY^T · X with dY [R, Nout] read in place (K-major) and X given TRANSPOSED, XT [Kin, rpad] (zero beyond
 // column R; rpad a multiple of 1024): the operand a cast / LayerNorm pass had to rewrite anyway.
 int wgrad_tn_launch(int dtype, const void* dY, long long ldy, const void* XT, long long rpad, long long R, int Nout, int Kin,
                     float* part, size_t part_bytes, int out_dtype, void* grad_out, int* counters, hipStream_t stream,
-                    const float* out_scale) {
+                    const float* out_scale, bool accumulate) {
     if (R <= 0 || Nout <= 0 || Kin % 256 != 0 || Nout % 8 != 0 || ldy % 8 != 0 || rpad % 1024 != 0 || rpad < R) {
         set_error("tp wgrad: unsupported shape R=%lld rpad=%lld Nout=%d Kin=%d", R, rpad, Nout, Kin);
         return TP_ERR_INVALID_ARG;
@@ -194,7 +198,7 @@ int wgrad_tn_launch(int dtype, const void* dY, long long ldy, const void* XT, lo
     a.M = Nout; a.N = Kin; a.K = (int)Ks; a.groups = S; a.tt_rows = R; a.tt_w_kcontig = 1; a.rows_per_batch = Nout; a.tile = 256;
     a.tile_counters = S <= 4 ? counters : nullptr;
     TP_TRY(gemm_launch(dtype, TP_F32, a, stream));
-    return bw_reduce_parts_launch(out_dtype, part, (long long)Nout * Kin, S, (long long)Nout * Kin, grad_out, stream, out_scale);
+    return bw_reduce_parts_launch(out_dtype, part, (long long)Nout * Kin, S, (long long)Nout * Kin, grad_out, stream, out_scale, accumulate);
 }
 
 }  // namespace tp
@@ -271,12 +275,48 @@ int tp_forward_train_parts(const tp_desc* desc, const void* x, const int64_t x_s
                         stream, nullptr, true, xm_parts);
 }
 
-// `ig` (tp_backward_inputs*; NULL for tp_backward*): the input gradients wanted — and then `grads` may be NULL (no parameter
-// gradients: every weight gradient, column sum and partial reduction is skipped; the dgrad chain, the attention backward and the
-// LayerNorm dx remain).
+// ---- what a backward has to run for the outputs that are wanted ----------------------------------------------------------
+// Fields of tp_grads by index (bit i of tp_backward_plan's `wanted_params`).
+enum { P_Q1W = 0, P_K0W, P_K0B, P_K2W, P_K2B, P_V0W, P_V0B, P_V2W, P_V2B, P_LNQW, P_LNQB, P_LNKW, P_LNKB, P_LNVW, P_LNVB,
+       P_INW, P_INB, P_OUTW, P_OUTB, P_M0W, P_M0B, P_M2W, P_M2B, P_COUNT };
+static_assert(sizeof(tp_grads) == P_COUNT * sizeof(void*), "tp_grads: 23 pointers");
+static_assert(sizeof(tp_grad_sink) == P_COUNT * sizeof(void*) + 8, "tp_grad_sink: tp_grads + two int32");
+static constexpr uint32_t pbit(int i) { return 1u << i; }
+
+uint32_t tp_backward_plan(uint32_t wanted, int want_dx, int want_dx_multi, int want_dmask) {
+    wanted &= (1u << P_COUNT) - 1;
+    auto any = [&](uint32_t m) { return (wanted & m) != 0; };
+    const bool dx = want_dx != 0, dxm = want_dx_multi != 0, dmask = want_dmask != 0;
+    const uint32_t k0 = pbit(P_K0W) | pbit(P_K0B), v0 = pbit(P_V0W) | pbit(P_V0B);
+    uint32_t plan = TP_BWD_STAGE_DY;
+    if (any(pbit(P_M2B))) plan |= TP_BWD_STAGE_MLP2_BIAS;
+    if (any(pbit(P_M2W))) plan |= TP_BWD_STAGE_MLP2_WGRAD;
+    if (any(pbit(P_M0B))) plan |= TP_BWD_STAGE_MLP0_BIAS;
+    if (any(pbit(P_M0W))) plan |= TP_BWD_STAGE_MLP0_WGRAD;
+    if (any(pbit(P_OUTB))) plan |= TP_BWD_STAGE_OUT_BIAS;
+    if (any(pbit(P_OUTW))) plan |= TP_BWD_STAGE_OUT_WGRAD;
+    if (any(k0 | v0)) plan |= TP_BWD_STAGE_KV0_WGRAD;
+    if (any(k0 | v0) || dxm) plan |= TP_BWD_STAGE_DZ1;
+    // a chain: the dgrad through the in-projection and the LayerNorm backward of one of q, k, v
+    if (any(pbit(P_LNQW) | pbit(P_LNQB) | pbit(P_INW) | pbit(P_Q1W)) || dx) plan |= TP_BWD_STAGE_Q_CHAIN;
+    if (any(pbit(P_LNKW) | pbit(P_LNKB) | pbit(P_K2W) | pbit(P_K2B) | k0 | pbit(P_INW)) || dxm) plan |= TP_BWD_STAGE_K_CHAIN;
+    if (any(pbit(P_LNVW) | pbit(P_LNVB) | pbit(P_V2W) | pbit(P_V2B) | v0 | pbit(P_INW)) || dxm) plan |= TP_BWD_STAGE_V_CHAIN;
+    // from here up the chain a stage runs when anything below it does
+    if ((plan & (TP_BWD_STAGE_Q_CHAIN | TP_BWD_STAGE_K_CHAIN | TP_BWD_STAGE_V_CHAIN)) || any(pbit(P_INB)) || dmask)
+        plan |= TP_BWD_STAGE_ATTENTION;
+    if (plan & TP_BWD_STAGE_ATTENTION) plan |= TP_BWD_STAGE_DO;
+    if (plan & (TP_BWD_STAGE_DO | TP_BWD_STAGE_OUT_BIAS | TP_BWD_STAGE_OUT_WGRAD)) plan |= TP_BWD_STAGE_DA1;
+    if (plan & (TP_BWD_STAGE_DA1 | TP_BWD_STAGE_MLP0_BIAS | TP_BWD_STAGE_MLP0_WGRAD)) plan |= TP_BWD_STAGE_DZ2;
+    return plan;
+}
+
+// `sink`: where the parameter gradients go (NULL, or every entry NULL: none — every weight gradient, column sum and partial
+// reduction is skipped); `strict`: the entry points older than tp_backward_sink, which refuse a NULL entry.  `ig`
+// (tp_backward_inputs*, tp_backward_masked, tp_backward_sink; NULL otherwise): the input gradients wanted.  What is launched
+// follows tp_backward_plan of what is wanted.
 static int backward_impl(const tp_desc* desc, const void* x_multi, const void* const* xm_parts, const int64_t xm_strides[3],
                          const tp_weights* raw, const void* packed_weights, const void* train_workspace, const void* dy,
-                         const tp_grads* grads, void* bw_workspace, size_t bw_workspace_bytes, void* stream_,
+                         const tp_grad_sink* sink, bool strict, void* bw_workspace, size_t bw_workspace_bytes, void* stream_,
                          const tp_input_grads* ig = nullptr, const tp_attn_mask* am = nullptr) {
     tp::TuningScope tuning_scope(desc);
     TP_TRY(validate_desc(desc));
@@ -297,16 +337,40 @@ static int backward_impl(const tp_desc* desc, const void* x_multi, const void* c
         return TP_ERR_INVALID_ARG;
     }
     float* const dmask = mask_mode ? am->grad : nullptr;
-    if (!x_multi || !xm_strides || !raw || !packed_weights || !train_workspace || !dy || (!grads && !ig && !dmask) || !bw_workspace) {
+    if (!x_multi || !xm_strides || !raw || !packed_weights || !train_workspace || !dy || (!sink && !ig && !dmask) || !bw_workspace) {
         set_error("tp_backward: NULL argument");
         return TP_ERR_INVALID_ARG;
     }
+    void* const* const gp = sink ? reinterpret_cast<void* const*>(&sink->grads) : nullptr;
+    uint32_t wanted = 0;                                // bit i: field i of tp_grads is wanted
     {
-        const void* const* gp = reinterpret_cast<const void* const*>(grads);
         const void* const* wp = reinterpret_cast<const void* const*>(raw);
-        for (size_t i = 0; i < sizeof(tp_grads) / sizeof(void*); ++i)
-            if ((grads && !gp[i]) || !wp[i]) { set_error("tp_backward: weight / gradient pointer #%zu is NULL", i); return TP_ERR_INVALID_ARG; }
+        for (size_t i = 0; i < P_COUNT; ++i) {
+            if ((sink && strict && !gp[i]) || !wp[i]) { set_error("tp_backward: weight / gradient pointer #%zu is NULL", i); return TP_ERR_INVALID_ARG; }
+            if (sink && gp[i]) wanted |= pbit((int)i);
+        }
     }
+    // the sink: element type of its entries (the model dtype, or fp32 — then they may accumulate)
+    const int OT = sink ? sink->dtype : desc->dtype;
+    const bool acc = sink && sink->accumulate != 0;
+    if (sink) {
+        if (OT != desc->dtype && OT != TP_F32) {
+            set_error("tp_backward_sink: sink dtype %d is neither the model dtype %d nor TP_F32", OT, desc->dtype);
+            return TP_ERR_INVALID_ARG;
+        }
+        if (sink->accumulate != 0 && (sink->accumulate != 1 || OT != TP_F32)) {
+            set_error("tp_backward_sink: accumulate = %d needs 0 or 1, and 1 an fp32 sink (dtype %d)", sink->accumulate, OT);
+            return TP_ERR_INVALID_ARG;
+        }
+        if (OT == TP_F32)
+            for (int i = 0; i < P_COUNT; ++i)
+                if ((uintptr_t)gp[i] & 15) { set_error("tp_backward_sink: fp32 gradient pointer #%d is not 16-byte aligned", i); return TP_ERR_INVALID_ARG; }
+        if (!wanted && !ig && !dmask) {
+            set_error("tp_backward_sink: nothing requested (every sink entry is NULL, no input and no mask gradient)");
+            return TP_ERR_INVALID_ARG;
+        }
+    }
+    auto G = [&](int i) -> void* { return gp ? gp[i] : nullptr; };
     // input gradients wanted: dx, dx_multi (one [B, N, 4096] tensor), dx_multi_parts (four [B, N, 1024])
     void* const dx = ig ? ig->dx : nullptr;
     void* const dxm = ig ? ig->dx_multi : nullptr;
@@ -317,18 +381,22 @@ static int backward_impl(const tp_desc* desc, const void* x_multi, const void* c
         if (nparts != 0 && nparts != 4) { set_error("tp_backward_inputs: dx_multi_parts must be all four or none"); return TP_ERR_INVALID_ARG; }
         if (nparts && !xm_parts) { set_error("tp_backward_inputs: dx_multi_parts belong to tp_backward_inputs_parts (use dx_multi)"); return TP_ERR_INVALID_ARG; }
         if (dxm && xm_parts) { set_error("tp_backward_inputs_parts: the gradient of four x_multi sources goes to dx_multi_parts"); return TP_ERR_INVALID_ARG; }
-        if (!dx && !dxm && !nparts && !grads && !dmask) { set_error("tp_backward_inputs: nothing requested (no input and no parameter gradients)"); return TP_ERR_INVALID_ARG; }
+        if (!dx && !dxm && !nparts && !wanted && !dmask) { set_error("tp_backward_inputs: nothing requested (no input and no parameter gradients)"); return TP_ERR_INVALID_ARG; }
         bool aligned = ((uintptr_t)dx & 15) == 0 && ((uintptr_t)dxm & 15) == 0;
         for (int i = 0; i < 4; ++i) aligned = aligned && ((uintptr_t)dxm_parts[i] & 15) == 0;
         if (!aligned) { set_error("tp_backward_inputs: dx / dx_multi must be 16-byte aligned"); return TP_ERR_INVALID_ARG; }
     }
     const bool want_dxm = dxm || dxm_parts[0];
-    const bool pg = grads != nullptr;                   // parameter gradients wanted
+    // what runs: ONE function decides it for this call and for a caller that asks in advance
+    const uint32_t plan = tp_backward_plan(wanted, dx != nullptr, want_dxm, dmask != nullptr);
+    auto runs = [&](uint32_t stage) { return (plan & stage) != 0; };
     if (desc->out_dtype != desc->dtype) { set_error("tp_backward: out_dtype must equal dtype"); return TP_ERR_INVALID_ARG; }
     const int B = desc->batch, g = desc->raw_grid, s = desc->scale_factor, D = desc->hidden_size;
-    // MT: the model dtype — weights, x_multi, dy and the parameter gradients.  GT: the dtype gradients TRAVEL in between the
-    // backward's kernels: fp16 behind a dynamic power-of-two scale for a bf16 model (bw_f16_chain), the model dtype otherwise.
+    // MT: the model dtype — weights, x_multi and dy.  OT (above): the dtype of the parameter gradients, MT unless the sink is fp32.
+    // GT: the dtype gradients TRAVEL in between the backward's kernels: fp16 behind a dynamic power-of-two scale for a bf16 model
+    // (bw_f16_chain), the model dtype otherwise.
     const int MT = desc->dtype;
+    const size_t osz = OT == TP_F32 ? 4 : 2;            // bytes per element of a parameter gradient
     const bool f16_chain = bw_f16_chain(desc);
     const int GT = f16_chain ? TP_F16 : MT;
     const int N = g * g, Gq = g / s, M = Gq * Gq, E = kEmbed;
@@ -380,10 +448,12 @@ static int backward_impl(const tp_desc* desc, const void* x_multi, const void* c
                  const float* gam = nullptr, const float* bet = nullptr, float* csum = nullptr) -> int {
         return bw_transpose_launch(sdt, GT, src, ld, rows, 0, rows, cols, dst, rpad, rpad, mr, gam, bet, csum, stream);
     };
-    // bias gradient from the column-sum partials the last transpose left behind
-    auto bias_grad = [&](int rpad, int cols, void* out) -> int {
-        return bw_reduce_many_parts_launch(MT, colpart, cols, rpad / 64, cols, out, redscratch, stream, inv_scale);
+    // a parameter gradient from fp32 partials, into the sink: many parts (column sums, LayerNorm partials) / few (split-K)
+    auto reduce_many = [&](const float* p, long long stride, int nparts, int n, void* out, const float* sc) -> int {
+        return bw_reduce_many_parts_launch(OT, p, stride, nparts, n, out, redscratch, stream, sc, -1, acc);
     };
+    // bias gradient from the column-sum partials the last transpose left behind
+    auto bias_grad = [&](int rpad, int cols, void* out) -> int { return reduce_many(colpart, cols, rpad / 64, cols, out, inv_scale); };
     // dX[rows, Kin] = dY[rows, Nout] · W[Nout, Kin]  with W^T [Kin, Nout] given
     auto dgrad = [&](const void* dY, long long ldy, int rows, int Nout, const void* WT, int Kin, void* dX, long long ldx,
                      int flags = 0, const void* Z = nullptr, long long ldz = 0, int out_dt = -1) -> int {
@@ -402,7 +472,7 @@ static int backward_impl(const tp_desc* desc, const void* x_multi, const void* c
         a.groups = S; a.a_gs = (long long)(rpad / S) * 2; a.w_gs = (long long)(rpad / S) * 2; a.c_gs = (long long)Nout * Kin * 4;
         a.tile = (Nout % 256 == 0 && Kin % 256 == 0) ? 0 : 128;      // auto: 256-tile persistent kernel once S * tiles fills the chip
         TP_TRY(launch(GT, TP_F32, a));
-        return bw_reduce_parts_launch(MT, part, (long long)Nout * Kin, S, (long long)Nout * Kin, grad_out, stream, inv_scale);
+        return bw_reduce_parts_launch(OT, part, (long long)Nout * Kin, S, (long long)Nout * Kin, grad_out, stream, inv_scale, acc);
     };
 
     // The same from dY in place (K-major GEMM operand, no dY^T): bias gradient by a column-sum pass over dY, weight
@@ -413,19 +483,19 @@ static int backward_impl(const tp_desc* desc, const void* x_multi, const void* c
     auto bias_grad_rows = [&](const void* dY, long long ldy, long long rows, int cols, void* out, int dt, const float* sc) -> int {
         const int slices = bw_colsum_rows_launch(dt, dY, ldy, rows, cols, colpart, stream);
         if (slices < 0) return slices;
-        return bw_reduce_many_parts_launch(MT, colpart, cols, slices, cols, out, redscratch, stream, sc);
+        return reduce_many(colpart, cols, slices, cols, out, sc);
     };
     auto wgrad_rows = [&](const void* dY, long long ldy, long long rows, int rpad, int Nout, int Kin, const void* X, long long ldx,
                           int x_dtype, char* XT_scratch, void* grad_out, const float* mr = nullptr, const float* gam = nullptr,
                           const float* bet = nullptr) -> int {
         const WgradX XR{X, ldx, 0, 0, nullptr, 0};
         if (x_dtype == GT && !mr && wgrad_tt_supported(rows, Nout, Kin, XR, ldy))
-            return wgrad_tt_launch(GT, dY, ldy, XR, rows, Nout, Kin, part, L.part_bytes, MT, grad_out, next_counters(), stream,
-                                   nullptr, 0, inv_scale);
+            return wgrad_tt_launch(GT, dY, ldy, XR, rows, Nout, Kin, part, L.part_bytes, OT, grad_out, next_counters(), stream,
+                                   nullptr, 0, inv_scale, acc);
         if (!XT_scratch) { set_error("tp_backward: a row-major operand the K-major weight gradient cannot read in place (rows %lld, %d x %d)", rows, Nout, Kin); return TP_ERR_INVALID_ARG; }
         TP_TRY(T(x_dtype, X, ldx, (int)rows, Kin, XT_scratch, rpad, mr, gam, bet));
-        return wgrad_tn_launch(GT, dY, ldy, XT_scratch, rpad, rows, Nout, Kin, part, L.part_bytes, MT, grad_out, next_counters(),
-                               stream, inv_scale);
+        return wgrad_tn_launch(GT, dY, ldy, XT_scratch, rpad, rows, Nout, Kin, part, L.part_bytes, OT, grad_out, next_counters(),
+                               stream, inv_scale, acc);
     };
     const bool inplace = (D % 256 == 0);                // (E = 1024 always is): every weight's Kin is a multiple of 256
 
@@ -452,13 +522,14 @@ static int backward_impl(const tp_desc* desc, const void* x_multi, const void* c
     }
 
     // ---- the incoming gradient: as it is, or (fp16 chain) scaled by a dynamic power of two and cast ----------------------
-    // (ONE pass over dy gives mlp[2]'s bias gradient — column sums of the unscaled dy — and max |dy| for the scale)
+    // (ONE pass over dy gives mlp[2]'s bias gradient — column sums of the unscaled dy — and max |dy| for the scale; a model-dtype
+    // chain that does not want that bias has nothing to take from the pass)
     const void* dyc = dy;                               // what the chain reads (dtype GT)
-    if (pg || f16_chain) {                              // (no parameter gradients: the pass still finds max |dy| for the scale)
+    if (runs(TP_BWD_STAGE_DY) && (runs(TP_BWD_STAGE_MLP2_BIAS) || f16_chain)) {
         int n_amax = 0;
         const int slices = bw_colsum_rows_launch(MT, dy, D, Rq, D, colpart, stream, f16_chain ? (float*)(bw + L.amaxpart) : nullptr, &n_amax);
         if (slices < 0) return slices;
-        if (pg) TP_TRY(bw_reduce_many_parts_launch(MT, colpart, D, slices, D, grads->mlp_2_bias, redscratch, stream, nullptr));
+        if (runs(TP_BWD_STAGE_MLP2_BIAS)) TP_TRY(reduce_many(colpart, D, slices, D, G(P_M2B), nullptr));
         if (f16_chain) {
             TP_TRY(bw_scale_from_partials_launch((const float*)(bw + L.amaxpart), n_amax, scale, stream));
             TP_TRY(bw_scale_cast_launch(MT, dy, (long long)Rq * D, scale, bw + L.dy16, stream, sat));
@@ -466,36 +537,39 @@ static int backward_impl(const tp_desc* desc, const void* x_multi, const void* c
         }
     }
     // ---- mlp[2] ---------------------------------------------------------------------------------------------
-    if (!pg) {
+    if (!runs(TP_BWD_STAGE_MLP2_WGRAD)) {
     } else if (inplace) {
-        TP_TRY(wgrad_rows(dyc, D, Rq, Rqp, D, D, fw + W.a2, D, TP_F16, bw + L.xt, grads->mlp_2_weight));
+        TP_TRY(wgrad_rows(dyc, D, Rq, Rqp, D, D, fw + W.a2, D, TP_F16, bw + L.xt, G(P_M2W)));
     } else {
         TP_TRY(T(GT, dyc, D, Rq, D, bw + L.dyT, Rqp));
         TP_TRY(T(TP_F16, fw + W.a2, D, Rq, D, bw + L.xt, Rqp));
-        TP_TRY(wgrad(bw + L.dyT, bw + L.xt, D, D, Rqp, grads->mlp_2_weight));
+        TP_TRY(wgrad(bw + L.dyT, bw + L.xt, D, D, Rqp, G(P_M2W)));
     }
+    if (!runs(TP_BWD_STAGE_DZ2)) return TP_OK;          // (only mlp[2]'s own gradients are wanted: no dgrad at all)
     TP_TRY(dgrad(dyc, D, Rq, D, bw + L.wt_m2, D, bw + L.dz2, D, TP_LINEAR_GELU_BWD, fw + W.z2, D));
     // ---- mlp[0] ---------------------------------------------------------------------------------------------
-    if (!pg) {
-    } else if (inplace) {
-        TP_TRY(bias_grad_rows(bw + L.dz2, D, Rq, D, grads->mlp_0_bias, GT, inv_scale));
-        TP_TRY(wgrad_rows(bw + L.dz2, D, Rq, Rqp, D, E, fw + W.a1, E, TP_F16, bw + L.xt, grads->mlp_0_weight));
-    } else {
+    if (inplace) {
+        if (runs(TP_BWD_STAGE_MLP0_BIAS)) TP_TRY(bias_grad_rows(bw + L.dz2, D, Rq, D, G(P_M0B), GT, inv_scale));
+        if (runs(TP_BWD_STAGE_MLP0_WGRAD)) TP_TRY(wgrad_rows(bw + L.dz2, D, Rq, Rqp, D, E, fw + W.a1, E, TP_F16, bw + L.xt, G(P_M0W)));
+    } else if (runs(TP_BWD_STAGE_MLP0_BIAS | TP_BWD_STAGE_MLP0_WGRAD)) {
         TP_TRY(T(GT, bw + L.dz2, D, Rq, D, bw + L.dz2T, Rqp, nullptr, nullptr, nullptr, colpart));
-        TP_TRY(bias_grad(Rqp, D, grads->mlp_0_bias));
-        TP_TRY(T(TP_F16, fw + W.a1, E, Rq, E, bw + L.xt, Rqp));
-        TP_TRY(wgrad(bw + L.dz2T, bw + L.xt, D, E, Rqp, grads->mlp_0_weight));
+        if (runs(TP_BWD_STAGE_MLP0_BIAS)) TP_TRY(bias_grad(Rqp, D, G(P_M0B)));
+        if (runs(TP_BWD_STAGE_MLP0_WGRAD)) {
+            TP_TRY(T(TP_F16, fw + W.a1, E, Rq, E, bw + L.xt, Rqp));
+            TP_TRY(wgrad(bw + L.dz2T, bw + L.xt, D, E, Rqp, G(P_M0W)));
+        }
     }
+    if (!runs(TP_BWD_STAGE_DA1)) return TP_OK;
     TP_TRY(dgrad(bw + L.dz2, D, Rq, D, bw + L.wt_m0, E, bw + L.da1, E));
     // ---- out_proj ---------------------------------------------------------------------------------------------
-    if (pg) {
-        TP_TRY(bias_grad_rows(bw + L.da1, E, Rq, E, grads->clip_attn_out_proj_bias, GT, inv_scale));
-        TP_TRY(wgrad_rows(bw + L.da1, E, Rq, Rqp, E, E, fw + W.o, E, TP_F16, bw + L.xt, grads->clip_attn_out_proj_weight));
-    }
+    if (runs(TP_BWD_STAGE_OUT_BIAS)) TP_TRY(bias_grad_rows(bw + L.da1, E, Rq, E, G(P_OUTB), GT, inv_scale));
+    if (runs(TP_BWD_STAGE_OUT_WGRAD)) TP_TRY(wgrad_rows(bw + L.da1, E, Rq, Rqp, E, E, fw + W.o, E, TP_F16, bw + L.xt, G(P_OUTW)));
+    if (!runs(TP_BWD_STAGE_DO)) return TP_OK;
     TP_TRY(dgrad(bw + L.da1, E, Rq, E, bw + L.wt_out, E, bw + L.dO, E));
     // ---- region attention ---------------------------------------------------------------------------------------
     // (masked: the mask in the recomputed logits, dL/dmask if asked for — mode 1's per-query partials in the split-K partial slab,
     // free between two weight gradients; every head's p still sums to 1, so in_proj_bias' v third below stays colsum(dO))
+    if (!runs(TP_BWD_STAGE_ATTENTION)) return TP_OK;    // (DO and ATTENTION run together; kept for the plan's sake)
     if (mask_mode)
         TP_TRY(bw_region_attention_masked_launch(GT, fw + W.q, fw + W.kv, fw + W.kv + kvE * 2, bw + L.dO, bw + L.dQ, bw + L.dKV,
                                                  bw + L.dKV + kvE * 2, B, g, s, stream, sat, am->mask, mask_mode, dmask, inv_scale,
@@ -503,10 +577,10 @@ static int backward_impl(const tp_desc* desc, const void* x_multi, const void* c
     else
         TP_TRY(bw_region_attention_launch(GT, fw + W.q, fw + W.kv, fw + W.kv + kvE * 2, bw + L.dO, bw + L.dQ, bw + L.dKV,
                                           bw + L.dKV + kvE * 2, B, g, s, stream, sat));
-    if (!pg && !ig) return TP_OK;                       // (dL/dmask only: nothing below the attention is wanted)
     // ---- attention in-projection (rows of in_proj_weight / in_proj_bias: q | k | v) --------------------------------
-    char* g_inw = pg ? (char*)grads->clip_attn_in_proj_weight : nullptr;
-    char* g_inb = pg ? (char*)grads->clip_attn_in_proj_bias : nullptr;
+    // (one tensor each: wanting it means all three of its thirds; byte offsets follow the sink's element size)
+    char* const g_inw = (char*)G(P_INW);
+    char* const g_inb = (char*)G(P_INB);
     // Per LayerNorm'd input (q, then k, v): bias gradient of its in-projection rows, dgrad through the in-projection, the
     // LayerNorm backward — which also leaves the LayerNorm's OUTPUT row-major in the gradient dtype (the in-projection's weight
     // gradient reads it in place: no transposing / normalising pass) and the column sums of its dx (the bias gradient of the layer
@@ -515,76 +589,86 @@ static int backward_impl(const tp_desc* desc, const void* x_multi, const void* c
     const int nb = 256;
     char* const xn = bw + L.xt;                          // the LayerNorm output of the moment [rows, E] (GT); consumed by the next launch
     //   q
-    if (pg) TP_TRY(bias_grad_rows(bw + L.dQ, E, Rq, E, g_inb, GT, inv_scale));
-    TP_TRY(dgrad(bw + L.dQ, E, Rq, E, bw + L.wt_in, E, bw + L.dq1, E));
-    TP_TRY(bw_ln_backward_launch(GT, bw + L.dq1, fw + W.q1pre, (const float*)(fw + W.mr_q), ln_g, bw + L.dQ1pre, lnpart, nb, Rq, stream,
-                                 ln_b, xn, sat));
-    if (pg) {
-        TP_TRY(bw_reduce_many_parts_launch(MT, lnpart, 3 * E, nb, E, grads->ln_q_1_weight, redscratch, stream, inv_scale));
-        TP_TRY(bw_reduce_many_parts_launch(MT, lnpart + E, 3 * E, nb, E, grads->ln_q_1_bias, redscratch, stream, inv_scale));
-        TP_TRY(wgrad_rows(bw + L.dQ, E, Rq, Rqp, E, E, xn, E, GT, nullptr, g_inw));
+    if (g_inb) TP_TRY(bias_grad_rows(bw + L.dQ, E, Rq, E, g_inb, GT, inv_scale));
+    if (runs(TP_BWD_STAGE_Q_CHAIN)) {
+        TP_TRY(dgrad(bw + L.dQ, E, Rq, E, bw + L.wt_in, E, bw + L.dq1, E));
+        TP_TRY(bw_ln_backward_launch(GT, bw + L.dq1, fw + W.q1pre, (const float*)(fw + W.mr_q), ln_g, bw + L.dQ1pre, lnpart, nb, Rq, stream,
+                                     ln_b, xn, sat));
+        if (G(P_LNQW)) TP_TRY(reduce_many(lnpart, 3 * E, nb, E, G(P_LNQW), inv_scale));
+        if (G(P_LNQB)) TP_TRY(reduce_many(lnpart + E, 3 * E, nb, E, G(P_LNQB), inv_scale));
+        if (g_inw) TP_TRY(wgrad_rows(bw + L.dQ, E, Rq, Rqp, E, E, xn, E, GT, nullptr, g_inw));
     }
     //   k, v (the K/V side feeds the parameter gradients and dx_multi only)
-    const bool kv_side = pg || want_dxm;
-    if (kv_side) {
-        void* gw[2] = {pg ? grads->ln_k_1_weight : nullptr, pg ? grads->ln_v_1_weight : nullptr};
-        void* gb[2] = {pg ? grads->ln_k_1_bias : nullptr, pg ? grads->ln_v_1_bias : nullptr};
-        void* gb2[2] = {pg ? grads->k_proj_1_2_bias : nullptr, pg ? grads->v_proj_1_2_bias : nullptr};
+    const uint32_t kv_chain[2] = {TP_BWD_STAGE_K_CHAIN, TP_BWD_STAGE_V_CHAIN};
+    {
+        void* gw[2] = {G(P_LNKW), G(P_LNVW)};
+        void* gb[2] = {G(P_LNKB), G(P_LNVB)};
+        void* gb2[2] = {G(P_K2B), G(P_V2B)};
         for (int t = 0; t < 2; ++t) {
             const char* dX = bw + L.dKV + (size_t)t * kvE * 2;
             // (in_proj_bias, v third: colsum(dV) = colsum(dO) — dv_j = p_j dO and every head's p sums to 1 over a region's keys — a
             // pass over the 4 x smaller [Rq, E] instead of [R, E]; k third: colsum(dK), mathematically zero, summed as it is stored)
-            if (!pg) {
-            } else if (t == 1) TP_TRY(bias_grad_rows(bw + L.dO, E, Rq, E, g_inb + (size_t)2 * E * 2, GT, inv_scale));
-            else TP_TRY(bias_grad_rows(dX, E, R, E, g_inb + (size_t)(1 + t) * E * 2, GT, inv_scale));
+            if (!g_inb) {
+            } else if (t == 1) TP_TRY(bias_grad_rows(bw + L.dO, E, Rq, E, g_inb + (size_t)2 * E * osz, GT, inv_scale));
+            else TP_TRY(bias_grad_rows(dX, E, R, E, g_inb + (size_t)(1 + t) * E * osz, GT, inv_scale));
+            if (!runs(kv_chain[t])) continue;
             TP_TRY(dgrad(dX, E, R, E, bw + L.wt_in + (size_t)(1 + t) * E * E * 2, E, bw + L.dkv1 + (size_t)t * kvE * 2, E));
             TP_TRY(bw_ln_backward_launch(GT, bw + L.dkv1 + (size_t)t * kvE * 2, fw + W.h2 + (size_t)t * kvE * 2,
                                          (const float*)(fw + W.mr_kv) + (size_t)t * R * 2, ln_g + (1 + t) * E,
                                          bw + L.dH2 + (size_t)t * kvE * 2, lnpart, nb, R, stream, ln_b + (1 + t) * E, xn, sat));
-            if (!pg) continue;
-            TP_TRY(bw_reduce_many_parts_launch(MT, lnpart, 3 * E, nb, E, gw[t], redscratch, stream, inv_scale));
-            TP_TRY(bw_reduce_many_parts_launch(MT, lnpart + E, 3 * E, nb, E, gb[t], redscratch, stream, inv_scale));
-            TP_TRY(bw_reduce_many_parts_launch(MT, lnpart + 2 * E, 3 * E, nb, E, gb2[t], redscratch, stream, inv_scale));   // colsum(dH2)
-            TP_TRY(wgrad_rows(dX, E, R, Rp, E, E, xn, E, GT, nullptr, g_inw + (size_t)(1 + t) * E * E * 2));
+            if (gw[t]) TP_TRY(reduce_many(lnpart, 3 * E, nb, E, gw[t], inv_scale));
+            if (gb[t]) TP_TRY(reduce_many(lnpart + E, 3 * E, nb, E, gb[t], inv_scale));
+            if (gb2[t]) TP_TRY(reduce_many(lnpart + 2 * E, 3 * E, nb, E, gb2[t], inv_scale));   // colsum(dH2)
+            if (g_inw) TP_TRY(wgrad_rows(dX, E, R, Rp, E, E, xn, E, GT, nullptr, g_inw + (size_t)(1 + t) * E * E * osz));
         }
     }
     // ---- q_proj_1 (no bias) ---------------------------------------------------------------------------------------
-    if (pg) TP_TRY(wgrad_rows(bw + L.dQ1pre, E, Rq, Rqp, E, E, fw + W.q0, E, TP_F16, bw + L.xt, grads->q_proj_1_weight));
+    if (G(P_Q1W)) TP_TRY(wgrad_rows(bw + L.dQ1pre, E, Rq, Rqp, E, E, fw + W.q0, E, TP_F16, bw + L.xt, G(P_Q1W)));
     // ---- k/v_proj_1[2] -----------------------------------------------------------------------------------------------
-    if (kv_side) {
-        void* gw[2] = {pg ? grads->k_proj_1_2_weight : nullptr, pg ? grads->v_proj_1_2_weight : nullptr};     // (the bias gradients: colsum(dH2) from the LayerNorm backward above)
+    {
+        void* gw[2] = {G(P_K2W), G(P_V2W)};              // (the bias gradients: colsum(dH2) from the LayerNorm backward above)
         for (int t = 0; t < 2; ++t) {
+            if (!runs(kv_chain[t])) continue;            // (no dH2 of this branch: nothing below it is wanted either)
             const char* dH = bw + L.dH2 + (size_t)t * kvE * 2;
             char* hT = bw + L.xt;
-            if (pg) TP_TRY(wgrad_rows(dH, E, R, Rp, E, E, fw + W.hkv + (size_t)t * E * 2, 2 * E, TP_F16, hT, gw[t]));
+            if (gw[t]) TP_TRY(wgrad_rows(dH, E, R, Rp, E, E, fw + W.hkv + (size_t)t * E * 2, 2 * E, TP_F16, hT, gw[t]));
             // (dZ1 leaves the chain in the MODEL dtype, still scaled by S: x_multi is in that dtype, and the first layer's weight
-            // gradient reads both in place)
-            TP_TRY(dgrad(dH, E, R, E, bw + L.wt_2 + (size_t)t * E * E * 2, E, bw + L.dZ1 + (size_t)t * E * 2, 2 * E,
-                         TP_LINEAR_GELU_BWD, fw + W.z1 + (size_t)t * E * 2, 2 * E, MT));
+            // gradient reads both in place.  A branch whose chain did not run leaves its half of dZ1 as the workspace holds it:
+            // columns of the joint first-layer contraction that nobody reduces)
+            if (runs(TP_BWD_STAGE_DZ1))
+                TP_TRY(dgrad(dH, E, R, E, bw + L.wt_2 + (size_t)t * E * E * 2, E, bw + L.dZ1 + (size_t)t * E * 2, 2 * E,
+                             TP_LINEAR_GELU_BWD, fw + W.z1 + (size_t)t * E * 2, 2 * E, MT));
         }
     }
     // ---- k/v_proj_1[0] -----------------------------------------------------------------------------------------------
     // dW0 [2E, 4096] = dZ1^T · x_multi (rows 0..E-1: k_proj_1[0], E..2E-1: v_proj_1[0]).  Both operands are in the model
     // dtype and row-major, so the contraction reads them in place (K-major GEMM operands): no dZ1^T, no x_multi^T.
+    // ONE launch serves both branches whichever of the four parameters are wanted (its split and summation order — the bits — stay
+    // those of the full backward); a parameter that is not wanted has its reduction skipped.
     auto first_layer_wgrad = [&]() -> int {
         const WgradX XM{x_multi, xm_strides[1], N, xm_strides[0], xm_parts, kMulti / 4};
         const bool xm_tt = wgrad_tt_supported(R, 2 * E, kMulti, XM, 2 * E);
+        const bool want_w = G(P_K0W) || G(P_V0W), want_b = G(P_K0B) || G(P_V0B);
         if (!xm_tt && L.xmT == kNoSlab) {               // (cannot happen for arguments tp_forward_train accepted)
             set_error("tp_backward: x_multi strides rule out the in-place weight gradient this workspace was sized for");
             return TP_ERR_INVALID_ARG;
         }
         if (xm_tt) {
-            const int slices = bw_colsum_rows_launch(MT, bw + L.dZ1, 2 * E, R, 2 * E, colpart, stream);
-            if (slices < 0) return slices;
-            TP_TRY(bw_reduce_many_parts_launch(MT, colpart, 2 * E, slices, E, grads->k_proj_1_0_bias, redscratch, stream, inv_scale));
-            TP_TRY(bw_reduce_many_parts_launch(MT, colpart + E, 2 * E, slices, E, grads->v_proj_1_0_bias, redscratch, stream, inv_scale));
+            if (want_b) {
+                const int slices = bw_colsum_rows_launch(MT, bw + L.dZ1, 2 * E, R, 2 * E, colpart, stream);
+                if (slices < 0) return slices;
+                if (G(P_K0B)) TP_TRY(reduce_many(colpart, 2 * E, slices, E, G(P_K0B), inv_scale));
+                if (G(P_V0B)) TP_TRY(reduce_many(colpart + E, 2 * E, slices, E, G(P_V0B), inv_scale));
+            }
+            if (!want_w) return TP_OK;
             int* ctr = (counters && launch_no < 64) ? counters + 32 * launch_no++ : nullptr;
-            return wgrad_tt_launch(MT, bw + L.dZ1, 2 * E, XM, R, 2 * E, kMulti, part, L.part_bytes, MT, grads->k_proj_1_0_weight,
-                                   ctr, stream, grads->v_proj_1_0_weight, E, inv_scale);
+            return wgrad_tt_launch(MT, bw + L.dZ1, 2 * E, XM, R, 2 * E, kMulti, part, L.part_bytes, OT, G(P_K0W),
+                                   ctr, stream, G(P_V0W), E, inv_scale, acc);
         }
         TP_TRY(bw_transpose_launch(MT, MT, bw + L.dZ1, 2 * E, R, 0, R, 2 * E, bw + L.dZ1T, Rp, Rp, nullptr, nullptr, nullptr, colpart, stream));
-        TP_TRY(bw_reduce_many_parts_launch(MT, colpart, 2 * E, Rp / 64, E, grads->k_proj_1_0_bias, redscratch, stream, inv_scale));
-        TP_TRY(bw_reduce_many_parts_launch(MT, colpart + E, 2 * E, Rp / 64, E, grads->v_proj_1_0_bias, redscratch, stream, inv_scale));
+        if (G(P_K0B)) TP_TRY(reduce_many(colpart, 2 * E, Rp / 64, E, G(P_K0B), inv_scale));
+        if (G(P_V0B)) TP_TRY(reduce_many(colpart + E, 2 * E, Rp / 64, E, G(P_V0B), inv_scale));
+        if (!want_w) return TP_OK;
         if (xm_parts) {                                 // four [B, N, 1024] sources -> rows part*1024 .. of x_multi^T
             for (int i = 0; i < 4; ++i)
                 TP_TRY(bw_transpose_launch(MT, MT, xm_parts[i], xm_strides[1], N, xm_strides[0], R, kMulti / 4,
@@ -601,13 +685,13 @@ static int backward_impl(const tp_desc* desc, const void* x_multi, const void* c
             a.ldw_bytes = (long long)Rp * 2;
             a.groups = S; a.a_gs = (long long)(Rp / S) * 2; a.w_gs = (long long)(Rp / S) * 2; a.c_gs = (long long)Nout * Kin * 4;
             TP_TRY(launch(MT, TP_F32, a));
-            TP_TRY(bw_reduce_parts_launch(MT, part, (long long)Nout * Kin, S, (long long)E * Kin, grads->k_proj_1_0_weight, stream, inv_scale));
-            TP_TRY(bw_reduce_parts_launch(MT, part + (size_t)E * Kin, (long long)Nout * Kin, S, (long long)E * Kin,
-                                          grads->v_proj_1_0_weight, stream, inv_scale));
+            if (G(P_K0W)) TP_TRY(bw_reduce_parts_launch(OT, part, (long long)Nout * Kin, S, (long long)E * Kin, G(P_K0W), stream, inv_scale, acc));
+            if (G(P_V0W)) TP_TRY(bw_reduce_parts_launch(OT, part + (size_t)E * Kin, (long long)Nout * Kin, S, (long long)E * Kin,
+                                                        G(P_V0W), stream, inv_scale, acc));
         }
         return TP_OK;
     };
-    if (pg) TP_TRY(first_layer_wgrad());
+    if (runs(TP_BWD_STAGE_KV0_WGRAD)) TP_TRY(first_layer_wgrad());
     if (!ig) return TP_OK;
 
     // ---- input gradients (tp_backward_inputs*) ---------------------------------------------------------------------------
@@ -648,27 +732,38 @@ static int backward_impl(const tp_desc* desc, const void* x_multi, const void* c
     return TP_OK;
 }
 
+// The entry points older than the gradient sink: a full sink in the model dtype that overwrites, every entry required.
+static int backward_all(const tp_desc* desc, const void* x_multi, const void* const* xm_parts, const int64_t xm_strides[3],
+                        const tp_weights* raw, const void* packed_weights, const void* train_workspace, const void* dy,
+                        const tp_grads* grads, void* bw_workspace, size_t bw_workspace_bytes, void* stream,
+                        const tp_input_grads* ig = nullptr, const tp_attn_mask* am = nullptr) {
+    tp_grad_sink sink{};
+    if (grads) { sink.grads = *grads; sink.dtype = desc ? desc->dtype : 0; sink.accumulate = 0; }
+    return backward_impl(desc, x_multi, xm_parts, xm_strides, raw, packed_weights, train_workspace, dy, grads ? &sink : nullptr, true,
+                         bw_workspace, bw_workspace_bytes, stream, ig, am);
+}
+
 int tp_backward(const tp_desc* desc, const void* x_multi, const int64_t xm_strides[3], const tp_weights* raw,
                 const void* packed_weights, const void* train_workspace, const void* dy, const tp_grads* grads,
                 void* bw_workspace, size_t bw_workspace_bytes, void* stream) {
-    return backward_impl(desc, x_multi, nullptr, xm_strides, raw, packed_weights, train_workspace, dy, grads,
-                         bw_workspace, bw_workspace_bytes, stream);
+    return backward_all(desc, x_multi, nullptr, xm_strides, raw, packed_weights, train_workspace, dy, grads,
+                        bw_workspace, bw_workspace_bytes, stream);
 }
 
 int tp_backward_parts(const tp_desc* desc, const void* const xm_parts[4], const int64_t part_strides[3],
                       const tp_weights* raw, const void* packed_weights, const void* train_workspace, const void* dy,
                       const tp_grads* grads, void* bw_workspace, size_t bw_workspace_bytes, void* stream) {
     if (!xm_parts) { set_error("tp_backward_parts: xm_parts is NULL"); return TP_ERR_INVALID_ARG; }
-    return backward_impl(desc, nullptr, xm_parts, part_strides, raw, packed_weights, train_workspace, dy, grads,
-                         bw_workspace, bw_workspace_bytes, stream);
+    return backward_all(desc, nullptr, xm_parts, part_strides, raw, packed_weights, train_workspace, dy, grads,
+                        bw_workspace, bw_workspace_bytes, stream);
 }
 
 int tp_backward_inputs(const tp_desc* desc, const void* x_multi, const int64_t xm_strides[3], const tp_weights* raw,
                        const void* packed_weights, const void* train_workspace, const void* dy, const tp_grads* grads,
                        const tp_input_grads* ig, void* bw_workspace, size_t bw_workspace_bytes, void* stream) {
     if (!ig) { set_error("tp_backward_inputs: ig is NULL"); return TP_ERR_INVALID_ARG; }
-    return backward_impl(desc, x_multi, nullptr, xm_strides, raw, packed_weights, train_workspace, dy, grads,
-                         bw_workspace, bw_workspace_bytes, stream, ig);
+    return backward_all(desc, x_multi, nullptr, xm_strides, raw, packed_weights, train_workspace, dy, grads,
+                        bw_workspace, bw_workspace_bytes, stream, ig);
 }
 
 int tp_backward_inputs_parts(const tp_desc* desc, const void* const xm_parts[4], const int64_t part_strides[3],
@@ -677,8 +772,8 @@ int tp_backward_inputs_parts(const tp_desc* desc, const void* const xm_parts[4],
                              void* stream) {
     if (!xm_parts) { set_error("tp_backward_inputs_parts: xm_parts is NULL"); return TP_ERR_INVALID_ARG; }
     if (!ig) { set_error("tp_backward_inputs_parts: ig is NULL"); return TP_ERR_INVALID_ARG; }
-    return backward_impl(desc, nullptr, xm_parts, part_strides, raw, packed_weights, train_workspace, dy, grads,
-                         bw_workspace, bw_workspace_bytes, stream, ig);
+    return backward_all(desc, nullptr, xm_parts, part_strides, raw, packed_weights, train_workspace, dy, grads,
+                        bw_workspace, bw_workspace_bytes, stream, ig);
 }
 
 int tp_backward_masked(const tp_desc* desc, const void* x_multi, const void* const xm_parts[4], const int64_t xm_strides[3],
@@ -686,8 +781,20 @@ int tp_backward_masked(const tp_desc* desc, const void* x_multi, const void* con
                        const tp_grads* grads, const tp_input_grads* ig, const tp_attn_mask* mask, void* bw_workspace,
                        size_t bw_workspace_bytes, void* stream) {
     if (!mask) { set_error("tp_backward_masked: mask is NULL"); return TP_ERR_INVALID_ARG; }
-    return backward_impl(desc, xm_parts ? nullptr : x_multi, xm_parts, xm_strides, raw, packed_weights, train_workspace, dy, grads,
-                         bw_workspace, bw_workspace_bytes, stream, ig, mask);
+    return backward_all(desc, xm_parts ? nullptr : x_multi, xm_parts, xm_strides, raw, packed_weights, train_workspace, dy, grads,
+                        bw_workspace, bw_workspace_bytes, stream, ig, mask);
+}
+
+int tp_backward_sink(const tp_desc* desc, const void* x_multi, const void* const xm_parts[4], const int64_t xm_strides[3],
+                     const tp_weights* raw, const void* packed_weights, const void* train_workspace, const void* dy,
+                     const tp_grad_sink* sink, const tp_input_grads* ig, const tp_attn_mask* mask, void* bw_workspace,
+                     size_t bw_workspace_bytes, void* stream) {
+    if (!sink && !ig && !(mask && mask->grad)) {
+        set_error("tp_backward_sink: nothing requested (no sink, no input gradients, no mask gradient)");
+        return TP_ERR_INVALID_ARG;
+    }
+    return backward_impl(desc, xm_parts ? nullptr : x_multi, xm_parts, xm_strides, raw, packed_weights, train_workspace, dy, sink,
+                         false, bw_workspace, bw_workspace_bytes, stream, ig, mask);
 }
 
 }  // extern "C"

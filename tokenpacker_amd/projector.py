@@ -36,7 +36,10 @@ _DTYPES = {torch.bfloat16: _capi.TP_BF16, torch.float16: _capi.TP_F16}
 
 class _ProjectFn(torch.autograd.Function):
     """Autograd node of the HIP projector: ``tp_forward_train`` keeps the backward's operands in a per-call
-    workspace, ``tp_backward`` returns the gradients of the 23 parameters.  The CLIP features come from a frozen
+    workspace, ``tp_backward_sink`` returns the gradients of those of the 23 parameters that require one (a frozen parameter gets a
+    NULL sink entry: its gradient is neither computed nor allocated, and whole stages of the backward drop out when nothing below them
+    is wanted — ``_capi.backward_plan``); with ``module.use_main_grad`` they are accumulated into the parameters' fp32 ``main_grad``
+    on the device instead, and autograd receives ``None``.  The CLIP features come from a frozen
     ``no_grad`` tower in the reference's recipe (clip_encoder.py:46, train.py:950-953) and get none — unless the module's
     ``input_gradients`` switch let them in requiring grad: then ``tp_backward_inputs*`` also returns dx / dx_multi, computing
     only what ``ctx.needs_input_grad`` asks for (no parameter gradients at all for a frozen projector).  With an ``attn_mask``
@@ -58,7 +61,7 @@ class _ProjectFn(torch.autograd.Function):
         n = ctx.n_parts
         xm, params = rest[:n], rest[n:]
         need = ctx.needs_input_grad                          # (module, x, mask, mask_mode, n_parts, *x_multi, *params)
-        want_dx, want_dmask, want_dxm, want_params = need[1], need[2], any(need[5:5 + n]), any(need[5 + n:])
+        want_dx, want_dmask, want_dxm, want_params = need[1], need[2], any(need[5:5 + n]), tuple(need[5 + n:])
         grads, dx, dxm, dmask = ctx.module._launch_backward(ctx.desc, xm[0] if n == 1 else xm, train_ws, packed, params, dy,
                                                             want_params=want_params, want_dx=want_dx, want_dxm=want_dxm,
                                                             mask=None if mask is None else (mask, ctx.mask_mode),
@@ -124,6 +127,15 @@ class TokenPacker(nn.Module):
         #: (tp_backward_inputs).  Default False, like the reference's recipe, whose tower is frozen and runs under no_grad
         #: (clip_encoder.py:46): inputs that require grad are refused.  Training-only, like every autograd use of the module.
         self.input_gradients = False
+        #: set True to accumulate the parameter gradients into fp32 ``p.main_grad`` buffers on the device (the Megatron / Apex /
+        #: Transformer Engine convention) instead of handing model-dtype gradients to autograd: every parameter that requires grad
+        #: must then carry ``p.main_grad`` — fp32, contiguous, 16-byte aligned, the parameter's shape, on its device
+        #: (``init_main_grads()`` makes them, ``zero_main_grads()`` clears them at the start of a step) — and every backward ADDS its
+        #: gradient to it, unrounded (micro-batch accumulation without the two roundings per micro-step of ``bf16 .grad += bf16 g``;
+        #: two calls of the module in one step both accumulate).  ``p.grad`` stays ``None``: autograd is told nothing about these
+        #: gradients, so DDP / ZeRO gradient hooks do NOT fire in this mode — the caller reduces ``main_grad`` across ranks itself.
+        #: Input and mask gradients are not affected.
+        self.use_main_grad = False
         #: fp32 callers.  The reference module runs in any dtype; the HIP kernels compute in bf16 / fp16 MFMA.  Under
         #: ``torch.autocast`` an fp32 module (fp32 master weights) is served in the autocast dtype like every
         #: ``nn.Linear`` of the reference would be.  Outside autocast an fp32 module is refused unless this names the
@@ -163,6 +175,7 @@ class TokenPacker(nn.Module):
             self.__dict__.setdefault(k, v)
         self.__dict__.setdefault("_workspaces", {})
         self.__dict__.setdefault("input_gradients", False)        # (modules pickled before the switch existed)
+        self.__dict__.setdefault("use_main_grad", False)
 
     def _reset_parameters(self) -> None:
         """Same initial distribution as the reference (builder.py:87-94): truncated normal
@@ -202,6 +215,51 @@ class TokenPacker(nn.Module):
                 "clip_attn.in_proj_weight": (3 * E, E), "clip_attn.in_proj_bias": (3 * E,),
                 "clip_attn.out_proj.weight": (E, E), "clip_attn.out_proj.bias": (E,),
                 "mlp.0.weight": (D, E), "mlp.0.bias": (D,), "mlp.2.weight": (D, D), "mlp.2.bias": (D,)}
+
+    # ---- fp32 main_grad (use_main_grad) -----------------------------------------------------------------------------
+    def init_main_grads(self) -> None:
+        """Give every parameter that requires grad a zeroed fp32 ``main_grad`` of its shape on its device (an existing one of the
+        right form is kept and zeroed).  Does not switch ``use_main_grad`` on."""
+        for p in self._named_weights():
+            if not p.requires_grad:
+                continue
+            mg = getattr(p, "main_grad", None)
+            if isinstance(mg, torch.Tensor) and mg.dtype == torch.float32 and mg.shape == p.shape and mg.device == p.device \
+                    and mg.is_contiguous() and mg.data_ptr() % 16 == 0:
+                mg.zero_()
+            else:
+                p.main_grad = torch.zeros(p.shape, dtype=torch.float32, device=p.device)
+
+    def zero_main_grads(self) -> None:
+        """Zero every parameter's ``main_grad`` (the start of an optimizer step; ``zero_grad`` does not know them)."""
+        for p in self._named_weights():
+            mg = getattr(p, "main_grad", None)
+            if isinstance(mg, torch.Tensor):
+                mg.zero_()
+
+    def check_main_grads(self):
+        """``use_main_grad``'s contract, checked before anything is launched: every parameter that requires grad carries a
+        ``main_grad`` that is an fp32 tensor (``TypeError`` otherwise) of the parameter's shape, contiguous, 16-byte aligned and on
+        the parameter's device (``ValueError``).  -> the list of (name, parameter, main_grad or None for a frozen parameter)."""
+        out = []
+        for name, p in zip(_capi.WEIGHT_FIELDS, self._named_weights()):
+            if not p.requires_grad:
+                out.append((name, p, None))
+                continue
+            mg = getattr(p, "main_grad", None)
+            if not isinstance(mg, torch.Tensor):
+                raise TypeError(f"use_main_grad: parameter {name} requires grad but has no main_grad tensor "
+                                f"(module.init_main_grads() allocates them)")
+            if mg.dtype != torch.float32:
+                raise TypeError(f"use_main_grad: {name}.main_grad is {mg.dtype}; it must be torch.float32")
+            if tuple(mg.shape) != tuple(p.shape):
+                raise ValueError(f"use_main_grad: {name}.main_grad has shape {tuple(mg.shape)}, the parameter {tuple(p.shape)}")
+            if mg.device != p.device:
+                raise ValueError(f"use_main_grad: {name}.main_grad is on {mg.device}, the parameter on {p.device}")
+            if not mg.is_contiguous() or mg.data_ptr() % 16:
+                raise ValueError(f"use_main_grad: {name}.main_grad must be contiguous and 16-byte aligned")
+            out.append((name, p, mg))
+        return out
 
     def _ln_eps(self) -> float:
         return float(self.ln_q_1.eps)
@@ -320,6 +378,8 @@ class TokenPacker(nn.Module):
         return torch.empty(0, dtype=dt, device=x.device), (self.num_queries, self.hidden_size)
 
     def forward(self, x, attn_mask=None, _stage_events=None, _out=None):
+        if self.use_main_grad and torch.is_grad_enabled():
+            self.check_main_grads()          # (a missing / ill-formed main_grad is named here, before anything is launched)
         x_multi = x[1]      # multi-level [B, N, 4096] — or its four [B, N, 1024] sources (tokenpacker_amd.tower)
         x = x[0]            # single-level [B, N, 1024]
         parts = None
@@ -391,7 +451,7 @@ class TokenPacker(nn.Module):
             if _stage_events is not None or self.output_fp32 or fp32_caller or _out is not None:
                 raise NotImplementedError("staged timing / fp32 output / fp32_compute_dtype / _out are inference-only")
             # (partially frozen projectors — e.g. LoRA-style experiments freezing the K/V branches — go through the same
-            # node: tp_backward computes every gradient, autograd drops those of parameters that do not require one)
+            # node: its backward asks tp_backward_sink for the gradients of the parameters that require one, and for nothing else)
             xm = x_multi if parts else (x_multi,)
             return _ProjectFn.apply(self, x, None if mask is None else mask[0], 0 if mask is None else mask[1], len(xm), *xm,
                                     *self._named_weights())
@@ -560,11 +620,16 @@ class TokenPacker(nn.Module):
 
     def _launch_backward(self, desc, x_multi, train_ws, packed, params, dy, want_params=True, want_dx=False, want_dxm=False,
                          mask=None, want_dmask=False):
-        """-> ``(parameter gradients or None, dx or None, dx_multi or None, dL/dmask or None)``, computing only what is asked for:
-        tp_backward* (parameters only), tp_backward_inputs* (``want_dx`` / ``want_dxm``) or, with the step's ``mask = (fp32 device
-        operand, mode)``, tp_backward_masked (``want_dmask``: the mask's own gradient).  dx_multi is one [B, N, 4096] tensor, or a
-        tuple of the four sources' [B, N, 1024] gradients when x_multi came as parts."""
+        """-> ``(parameter gradients or None, dx or None, dx_multi or None, dL/dmask or None)``, computing only what is asked for
+        through ONE entry point, tp_backward_sink: ``want_params`` is a bool (all or none) or one bool per parameter in tp_weights
+        order — a parameter that is not wanted gets a NULL sink entry and ``None``, and no buffer; ``want_dx`` / ``want_dxm`` the
+        input gradients; with the step's ``mask = (fp32 device operand, mode)``, ``want_dmask`` the mask's own gradient.  With
+        ``use_main_grad`` the wanted parameter gradients are added to the parameters' fp32 ``main_grad`` (fp32 sink, accumulate)
+        and every returned parameter gradient is ``None``.  dx_multi is one [B, N, 4096] tensor, or a tuple of the four sources'
+        [B, N, 1024] gradients when x_multi came as parts."""
         inputs = want_dx or want_dxm
+        wanted = [bool(want_params)] * len(params) if isinstance(want_params, bool) else [bool(w) for w in want_params]
+        main = self.check_main_grads() if (self.use_main_grad and any(wanted)) else None
         parts = tuple(x_multi) if isinstance(x_multi, (tuple, list)) else None
         if parts:
             x_multi = parts[0]
@@ -576,9 +641,18 @@ class TokenPacker(nn.Module):
             # compute dtype for the dgrad operands exactly as they were for the forward
             contiguous = [p.detach().to(x_multi.dtype).contiguous() for p in params]
             raw = _capi.tp_weights(*[t.data_ptr() for t in contiguous])
-            grads = [torch.empty_like(t) for t in contiguous] if want_params else None
-            gptr = _capi.tp_grads(*[t.data_ptr() for t in grads]) if want_params else None
-            g_arg = ctypes.byref(gptr) if want_params else None
+            grads = sink = None
+            if main is not None:                 # (the parameters as they are NOW: the ones whose main_grad the caller reads)
+                targets = [mg if w else None for w, (_, _, mg) in zip(wanted, main)]
+                if any(w and t is None for w, t in zip(wanted, targets)):
+                    raise RuntimeError("use_main_grad: a parameter's requires_grad changed between the forward and the backward")
+                sink = _capi.tp_grad_sink(_capi.tp_grads(*[t.data_ptr() if t is not None else None for t in targets]),
+                                          _capi.TP_F32, 1)
+            elif any(wanted):
+                grads = [torch.empty_like(t) if w else None for t, w in zip(contiguous, wanted)]
+                sink = _capi.tp_grad_sink(_capi.tp_grads(*[t.data_ptr() if t is not None else None for t in grads]),
+                                          _DTYPES[x_multi.dtype], 0)
+            g_arg = ctypes.byref(sink) if sink is not None else None
             bw_bytes = (lib.tp_backward_inputs_workspace_bytes if inputs else lib.tp_backward_workspace_bytes)(ctypes.byref(desc))
             if bw_bytes == 0:
                 raise RuntimeError(f"tp_backward_workspace_bytes: {_capi.last_error()}")
@@ -600,34 +674,18 @@ class TokenPacker(nn.Module):
                     ig.dx_multi = dxm.data_ptr()
             part_ptrs = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in parts]) if parts else None
             xm_strides = _capi.strides3((parts[0] if parts else x_multi).stride())
+            am = None
             if mask is not None:
                 dmask = torch.empty_like(mask[0]) if want_dmask else None
                 am = _capi.tp_attn_mask(mask=mask[0].data_ptr(), mode=mask[1], reserved=0,
                                         grad=dmask.data_ptr() if want_dmask else None)
-                _capi.check(lib.tp_backward_masked(ctypes.byref(desc), None if parts else x_multi.data_ptr(), part_ptrs,
-                                                   xm_strides, ctypes.byref(raw), packed.data_ptr(), train_ws.data_ptr(),
-                                                   dy.data_ptr(), g_arg, ctypes.byref(ig) if inputs else None, ctypes.byref(am),
-                                                   bw.data_ptr(), bw.numel(), stream_ptr), "tp_backward_masked")
-            elif inputs and parts:
-                _capi.check(lib.tp_backward_inputs_parts(ctypes.byref(desc), part_ptrs, xm_strides, ctypes.byref(raw),
-                                                         packed.data_ptr(), train_ws.data_ptr(), dy.data_ptr(), g_arg,
-                                                         ctypes.byref(ig), bw.data_ptr(), bw.numel(), stream_ptr),
-                            "tp_backward_inputs_parts")
-            elif inputs:
-                _capi.check(lib.tp_backward_inputs(ctypes.byref(desc), x_multi.data_ptr(), xm_strides, ctypes.byref(raw),
-                                                   packed.data_ptr(), train_ws.data_ptr(), dy.data_ptr(), g_arg, ctypes.byref(ig),
-                                                   bw.data_ptr(), bw.numel(), stream_ptr), "tp_backward_inputs")
-            elif parts:
-                _capi.check(lib.tp_backward_parts(ctypes.byref(desc), part_ptrs, xm_strides, ctypes.byref(raw), packed.data_ptr(),
-                                                  train_ws.data_ptr(), dy.data_ptr(), g_arg, bw.data_ptr(), bw.numel(),
-                                                  stream_ptr), "tp_backward_parts")
-            else:
-                _capi.check(lib.tp_backward(ctypes.byref(desc), x_multi.data_ptr(), xm_strides, ctypes.byref(raw),
-                                            packed.data_ptr(), train_ws.data_ptr(), dy.data_ptr(), g_arg, bw.data_ptr(),
-                                            bw.numel(), stream_ptr), "tp_backward")
+            _capi.check(lib.tp_backward_sink(ctypes.byref(desc), None if parts else x_multi.data_ptr(), part_ptrs, xm_strides,
+                                             ctypes.byref(raw), packed.data_ptr(), train_ws.data_ptr(), dy.data_ptr(), g_arg,
+                                             ctypes.byref(ig) if inputs else None, ctypes.byref(am) if am is not None else None,
+                                             bw.data_ptr(), bw.numel(), stream_ptr), "tp_backward_sink")
             self._watch_backward_status(bw, device)
         if grads is not None:
-            grads = [g if g.dtype == p.dtype else g.to(p.dtype) for g, p in zip(grads, params)]
+            grads = [g if g is None or g.dtype == p.dtype else g.to(p.dtype) for g, p in zip(grads, params)]
         return grads, dx, dxm, dmask
 
     def backward_saturated(self) -> int:

@@ -14,6 +14,8 @@ inputs requiring grad) and prices the two extra dgrads: dx_multi = dZ1 · [Wk0; 
 --mask also times the step with an attn_mask that is a learnable region bias (a float mask requiring grad: the masked attention
 backward and dL/dmask): the 2-D [1, s*s] form (dmask summed over every image, query and head) and the 3-D [(M*B)*8, 1, s*s]
 form (every entry written once).
+--trainable not_kv / mlp times the step of a partially frozen projector (the K/V branches frozen; only mlp.* trainable): the backward
+computes the gradients of the parameters that require one and nothing else (tp_backward_sink).  HIP only: no eager baseline.
 """
 import argparse
 import json
@@ -68,6 +70,8 @@ def main():
     ap.add_argument("--optimizer", default="sgd", choices=["sgd", "none"])
     ap.add_argument("--input-grads", action="store_true", help="also time the step with gradients with respect to x / x_multi")
     ap.add_argument("--mask", action="store_true", help="also time the step with a learnable attn_mask (2-D and 3-D float)")
+    ap.add_argument("--trainable", default="all", choices=["all", "not_kv", "mlp"],
+                    help="freeze the K/V branches (k_proj_1, v_proj_1, ln_k_1, ln_v_1), or everything but mlp.* (implies --hip-only)")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE", help="library tuning knob, e.g. BWD_CHAIN=1")
     args = ap.parse_args()
     from tokenpacker_amd import _capi
@@ -75,10 +79,15 @@ def main():
         key, val = kv.split("=")
         _capi.set_tuning(getattr(_capi, "TP_TUNE_" + key.upper()), int(val))
     s, D, dtype = args.scale_factor, args.hidden_size, torch.bfloat16
+    args.hip_only = args.hip_only or args.trainable != "all"
+    frozen = {"all": (), "not_kv": ("k_proj_1.", "v_proj_1.", "ln_k_1.", "ln_v_1."), "mlp": ("",)}[args.trainable]
     results = []
     for B in args.batches:
         torch.manual_seed(0)
         m = TokenPacker(hidden_size=D, scale_factor=s).to(device="cuda", dtype=dtype)
+        for name, p in m.named_parameters():
+            if name.startswith(frozen) and not (args.trainable == "mlp" and name.startswith("mlp.")):
+                p.requires_grad_(False)
         g = torch.Generator(device="cuda").manual_seed(1)
         x = torch.randn(B, 576, 1024, generator=g, device="cuda").to(dtype)
         xm = torch.randn(B, 576, 4096, generator=g, device="cuda").to(dtype)
@@ -86,7 +95,7 @@ def main():
 
         import copy
         m_eager = copy.deepcopy(m)                       # each pipeline trains its own copy of the weights
-        opt = torch.optim.SGD(m.parameters(), lr=1e-7) if args.optimizer == "sgd" else None
+        opt = torch.optim.SGD([p for p in m.parameters() if p.requires_grad], lr=1e-7) if args.optimizer == "sgd" else None
         opt_e = torch.optim.SGD(m_eager.parameters(), lr=1e-7) if args.optimizer == "sgd" else None
 
         def step_hip():
@@ -149,7 +158,7 @@ def main():
         # (ln_k_1.bias and the k third of in_proj_bias have a mathematically zero gradient: round-off in both)
         E = 1024
         if args.hip_only:
-            rec = {"B": B, "hip_fwd_bwd_ms": round(ms_hip, 3), "hip_fwd_only_ms": round(ms_fwd, 3), **ig}
+            rec = {"B": B, "trainable": args.trainable, "hip_fwd_bwd_ms": round(ms_hip, 3), "hip_fwd_only_ms": round(ms_fwd, 3), **ig}
             print(json.dumps(rec), flush=True)
             results.append(rec)
             del m, x, xm, w, x_in, xm_in, masks
