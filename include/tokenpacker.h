@@ -39,6 +39,8 @@ extern "C" {
  * tp_backward_masked (training with an attn_mask, and its gradient).  Nothing else changes. */
 /* ABI 6, extended again (by symbol, the version stays 6): tp_grad_sink, tp_backward_sink and tp_backward_plan (a backward that skips
  * the gradients of frozen parameters and can accumulate into fp32 buffers).  Every older entry point keeps its behaviour and its bits. */
+/* ABI 6, extended a third time (by symbol, the version stays 6): tp_optim_tensor, tp_optim_hyper, tp_optim_state,
+ * tp_optim_workspace_bytes and tp_optim_step (gradient clipping and AdamW on those fp32 buffers).  Nothing else changes. */
 #define TP_ABI_VERSION 6
 
 typedef enum tp_status {
@@ -461,6 +463,69 @@ int tp_backward_sink(const tp_desc* desc, const void* x_multi, const void* const
                      const tp_grad_sink* sink, const tp_input_grads* ig, const tp_attn_mask* mask, void* bw_workspace,
                      size_t bw_workspace_bytes, void* stream);
 uint32_t tp_backward_plan(uint32_t wanted_params, int want_dx, int want_dx_multi, int want_dmask);
+
+/* ---- optimizer step: clip + AdamW on the fp32 gradient buffers (ABI 6 extension, detected by symbol) ----------------------
+ * The consumer of what tp_backward_sink accumulates (sink dtype TP_F32, accumulate 1): the reference's stage-1 recipe —
+ * `optim = "adamw_torch"` (train.py:81) behind HF's max_grad_norm clipping, per-group lr / weight_decay (llava_trainer.py:164-222) —
+ * as three launches per table of up to 32 tensors: the global L2 norm of grad * inv_scale, the clipping coefficient and overflow
+ * guard, then torch.optim.AdamW's update (no amsgrad, no maximize) on fp32 master weights with the model-dtype write-back and the
+ * zeroing of the gradient buffers.  Per element, with g = grad * inv_scale * clip_coef, in fp32:
+ *     p <- p * (1 - lr * weight_decay);  m <- beta1 * m + (1 - beta1) * g;  v <- beta2 * v + (1 - beta2) * g * g;
+ *     p <- p - (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps),      bc_i = 1 - beta_i ^ step
+ * master, exp_avg and exp_avg_sq are stored in fp32, param as the round-to-nearest-even cast of the stored master (no clamp: what
+ * Tensor.to does).  Work is cut into chunks of a fixed number of elements and every sum runs in a fixed order: no atomics, results
+ * do not depend on the device's CU count, two runs give the same bits.  A table longer than 32 entries is served by consecutive
+ * launches.  Enqueue-only, reentrant, allocates nothing.
+ *
+ *   tp_optim_tensor  one tensor: param (hyper.dtype), master / grad / exp_avg / exp_avg_sq (fp32), all of numel elements, and the
+ *                    lr / weight_decay of its parameter group.  The 16-byte vector path needs all five pointers 16-byte aligned
+ *                    and numel % 4 == 0; everything else (element alignment is the minimum) takes a scalar path.
+ *   tp_optim_hyper   beta1, beta2 in [0, 1); eps >= 0; max_grad_norm <= 0 or +inf: no clipping (the norm and found_inf are
+ *                    computed all the same); dtype TP_BF16 / TP_F16; flags 0 | TP_OPTIM_ZERO_GRAD (grad is zeroed behind the
+ *                    update — on a skipped step too).
+ *   inv_scale        device float (the reciprocal of a loss scale; read by the kernels, never by the host), or NULL: 1.
+ *   state            tp_optim_state, a device block of TP_OPTIM_STATE_BYTES the caller zeroes ONCE and keeps across steps:
+ *                      grad_norm  the norm of grad * inv_scale before clipping, summed in fp32 per chunk, in fp64 across chunks
+ *                      clip_coef  min(1, max_grad_norm / (grad_norm + 1e-6)) in fp32 (clip_grad_norm_'s formula); 1 without
+ *                                 clipping, 0 on a skipped step
+ *                      found_inf  1 when grad_norm is not finite: THIS step was skipped — master, exp_avg, exp_avg_sq and param
+ *                                 keep their bits (gradients whose fp32 sum of squares overflows count as non-finite)
+ *                      step       steps applied so far; a skipped step does not advance it (torch's fused AdamW under a GradScaler)
+ *                      skipped    steps skipped so far
+ *                      bc1, sqrt_bc2   1 - beta1^step and sqrt(1 - beta2^step) of the step being applied, computed on the device
+ *                                 in fp64 from `step`, stored as fp32
+ *   workspace        tp_optim_workspace_bytes bytes, 16-byte aligned: one fp32 partial sum per chunk, plus room for a state block
+ *                    behind them (a caller may place `state` in the last TP_OPTIM_STATE_BYTES of the same allocation); 0 with
+ *                    the error set on a bad table.
+ * TP_ERR_INVALID_ARG before anything is enqueued, the message naming the entry: n < 0, a NULL pointer, numel <= 0, a pointer not
+ * aligned to its element size, the same address twice among all pointers of the table, a beta outside [0, 1), negative or
+ * non-finite eps / lr / weight_decay, a dtype other than bf16 / fp16, unknown flags, a workspace that is too small.  n == 0 is
+ * TP_OK and launches nothing. */
+enum { TP_OPTIM_ZERO_GRAD = 1 };
+typedef struct tp_optim_tensor {
+    void* param; float* master; float* grad; float* exp_avg; float* exp_avg_sq;
+    int64_t numel;
+    float lr; float weight_decay;
+} tp_optim_tensor;
+typedef struct tp_optim_hyper {
+    float beta1, beta2, eps, max_grad_norm;
+    int32_t dtype;
+    uint32_t flags;
+} tp_optim_hyper;
+#define TP_OPTIM_STATE_BYTES 64
+typedef struct tp_optim_state {
+    float   grad_norm;     /* byte  0 */
+    float   clip_coef;     /* byte  4 */
+    int32_t found_inf;     /* byte  8 */
+    int32_t step;          /* byte 12 */
+    int32_t skipped;       /* byte 16 */
+    float   bc1;           /* byte 20 */
+    float   sqrt_bc2;      /* byte 24 */
+    int32_t reserved[9];   /* stays zero */
+} tp_optim_state;
+size_t tp_optim_workspace_bytes(const tp_optim_tensor* t, int n);
+int tp_optim_step(const tp_optim_tensor* t, int n, const tp_optim_hyper* h, const float* inv_scale, void* state, void* workspace,
+                  size_t workspace_bytes, void* stream);
 
 /* The backward's weight-gradient contraction on its own (what autograd computes for every nn.Linear of
  * builder.py:59-83):  dw[n_out, k_in] = sum over the `rows` token rows of dy[r, n] * x[r, k], read from the ROW-MAJOR

@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = (
     "tp_backward_inputs_workspace_bytes", "tp_backward_inputs", "tp_backward_inputs_parts",
     "tp_forward_train_masked", "tp_forward_parts_masked", "tp_backward_masked",
     "tp_backward_sink", "tp_backward_plan",
+    "tp_optim_workspace_bytes", "tp_optim_step",
     "tp_hd_assemble_backward_workspace_bytes", "tp_hd_assemble_backward",
     "tp_splice", "tp_splice_backward_workspace_bytes", "tp_splice_backward",
     "tp_tuning_create", "tp_tuning_destroy", "tp_tuning_set", "tp_tuning_get", "tp_gather_alloc_flags", "tp_gather_free_flags", "tp_gather_export", "tp_gather_open", "tp_gather_close", "tp_gather_push", "tp_gather_sync",
@@ -121,6 +122,28 @@ class tp_grad_sink(Structure):
     """Where tp_backward_sink puts the parameter gradients: one pointer per parameter (NULL = not wanted, nothing is computed for it
     alone), the element type of the non-NULL entries (the model dtype or TP_F32) and whether they accumulate (TP_F32 only)."""
     _fields_ = [("grads", tp_grads), ("dtype", c_int32), ("accumulate", c_int32)]
+
+
+TP_OPTIM_ZERO_GRAD = 1
+TP_OPTIM_STATE_BYTES = 64
+
+
+class tp_optim_tensor(Structure):
+    """One tensor of tp_optim_step's table: the model-dtype parameter, its fp32 master / gradient / moments, its element count
+    and its parameter group's lr / weight_decay."""
+    _fields_ = [("param", c_void_p), ("master", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p),
+                ("numel", c_int64), ("lr", c_float), ("weight_decay", c_float)]
+
+
+class tp_optim_hyper(Structure):
+    _fields_ = [("beta1", c_float), ("beta2", c_float), ("eps", c_float), ("max_grad_norm", c_float), ("dtype", c_int32),
+                ("flags", c_uint32)]
+
+
+class tp_optim_state(Structure):
+    """The device state block of tp_optim_step (TP_OPTIM_STATE_BYTES; the fixed layout of include/tokenpacker.h)."""
+    _fields_ = [("grad_norm", c_float), ("clip_coef", c_float), ("found_inf", c_int32), ("step", c_int32), ("skipped", c_int32),
+                ("bc1", c_float), ("sqrt_bc2", c_float), ("reserved", c_int32 * 9)]
 
 
 # tp_backward_plan's result: which stages a backward runs for what is wanted (include/tokenpacker.h)
@@ -291,6 +314,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                      POINTER(tp_attn_mask), c_void_p, c_size_t, c_void_p]
     lib.tp_backward_plan.restype = c_uint32
     lib.tp_backward_plan.argtypes = [c_uint32, c_int, c_int, c_int]
+    lib.tp_optim_workspace_bytes.restype = c_size_t
+    lib.tp_optim_workspace_bytes.argtypes = [POINTER(tp_optim_tensor), c_int]
+    lib.tp_optim_step.restype = c_int
+    lib.tp_optim_step.argtypes = [POINTER(tp_optim_tensor), c_int, POINTER(tp_optim_hyper), c_void_p, c_void_p, c_void_p, c_size_t,
+                                  c_void_p]
     lib.tp_wgrad_workspace_bytes.restype = c_size_t
     lib.tp_wgrad_workspace_bytes.argtypes = [c_int, c_int]
     lib.tp_wgrad.restype = c_int

@@ -71,6 +71,25 @@ class _ProjectFn(torch.autograd.Function):
         return (None, dx, dmask, None, None) + dxm + (tuple(grads) if grads is not None else (None,) * len(params))
 
 
+def checked_main_grad(name: str, p: torch.Tensor) -> torch.Tensor:
+    """The ``main_grad`` of a parameter that requires grad, or the named error of ``use_main_grad``'s contract: an fp32 tensor
+    (``TypeError`` otherwise) of the parameter's shape, contiguous, 16-byte aligned and on the parameter's device (``ValueError``).
+    ``TokenPacker.check_main_grads`` and ``tokenpacker_amd.optim.MainGradAdamW`` both hold their parameters to it."""
+    mg = getattr(p, "main_grad", None)
+    if not isinstance(mg, torch.Tensor):
+        raise TypeError(f"use_main_grad: parameter {name} requires grad but has no main_grad tensor "
+                        f"(module.init_main_grads() allocates them)")
+    if mg.dtype != torch.float32:
+        raise TypeError(f"use_main_grad: {name}.main_grad is {mg.dtype}; it must be torch.float32")
+    if tuple(mg.shape) != tuple(p.shape):
+        raise ValueError(f"use_main_grad: {name}.main_grad has shape {tuple(mg.shape)}, the parameter {tuple(p.shape)}")
+    if mg.device != p.device:
+        raise ValueError(f"use_main_grad: {name}.main_grad is on {mg.device}, the parameter on {p.device}")
+    if not mg.is_contiguous() or mg.data_ptr() % 16:
+        raise ValueError(f"use_main_grad: {name}.main_grad must be contiguous and 16-byte aligned")
+    return mg
+
+
 def _forget_packed(ptr: int) -> None:
     try:
         _capi.load_library().tp_pack_forget(ptr)
@@ -246,19 +265,7 @@ class TokenPacker(nn.Module):
             if not p.requires_grad:
                 out.append((name, p, None))
                 continue
-            mg = getattr(p, "main_grad", None)
-            if not isinstance(mg, torch.Tensor):
-                raise TypeError(f"use_main_grad: parameter {name} requires grad but has no main_grad tensor "
-                                f"(module.init_main_grads() allocates them)")
-            if mg.dtype != torch.float32:
-                raise TypeError(f"use_main_grad: {name}.main_grad is {mg.dtype}; it must be torch.float32")
-            if tuple(mg.shape) != tuple(p.shape):
-                raise ValueError(f"use_main_grad: {name}.main_grad has shape {tuple(mg.shape)}, the parameter {tuple(p.shape)}")
-            if mg.device != p.device:
-                raise ValueError(f"use_main_grad: {name}.main_grad is on {mg.device}, the parameter on {p.device}")
-            if not mg.is_contiguous() or mg.data_ptr() % 16:
-                raise ValueError(f"use_main_grad: {name}.main_grad must be contiguous and 16-byte aligned")
-            out.append((name, p, mg))
+            out.append((name, p, checked_main_grad(name, p)))
         return out
 
     def _ln_eps(self) -> float:

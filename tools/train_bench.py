@@ -2,7 +2,9 @@
 """Training-step timing of the projector on one MI355X: HIP forward+backward (tp_forward_train / tp_backward
 through the autograd node) next to the reference's op sequence under PyTorch-ROCm eager autograd
 (oracle/reference_ops.py).  Batch 32 is the reference's per-GPU pretraining batch (scripts/v1_5/pretrain.sh:19).
-A step is forward + backward + OPTIMIZER STEP (plain SGD on the 23 parameters, `--optimizer none` to leave it out):
+A step is forward + backward + OPTIMIZER STEP (plain SGD on the 23 parameters; `--optimizer none` leaves it out;
+`--optimizer main_grad_adamw` is the reference's recipe instead — the backward into fp32 main_grad, then clipping + AdamW on fp32
+masters in one call, tokenpacker_amd.optim.MainGradAdamW; the eager side then runs clip_grad_norm_ + torch.optim.AdamW):
 the weight update is what makes the next forward re-pack the kernel-side weight image (casts, LayerNorm folds) and
 the backward re-transpose the weights, so it belongs inside the timed step.  FLOPs are priced on the work the
 backward actually has to do: no input gradient for k/v_proj_1[0] (the CLIP features come from a frozen tower).
@@ -67,7 +69,7 @@ def main():
     ap.add_argument("--hidden-size", type=int, default=4096)
     ap.add_argument("--out", default="gpurun_out/train_bench.json")
     ap.add_argument("--hip-only", action="store_true", help="skip the eager baseline (profiling runs)")
-    ap.add_argument("--optimizer", default="sgd", choices=["sgd", "none"])
+    ap.add_argument("--optimizer", default="sgd", choices=["sgd", "none", "main_grad_adamw"])
     ap.add_argument("--input-grads", action="store_true", help="also time the step with gradients with respect to x / x_multi")
     ap.add_argument("--mask", action="store_true", help="also time the step with a learnable attn_mask (2-D and 3-D float)")
     ap.add_argument("--trainable", default="all", choices=["all", "not_kv", "mlp"],
@@ -97,6 +99,14 @@ def main():
         m_eager = copy.deepcopy(m)                       # each pipeline trains its own copy of the weights
         opt = torch.optim.SGD([p for p in m.parameters() if p.requires_grad], lr=1e-7) if args.optimizer == "sgd" else None
         opt_e = torch.optim.SGD(m_eager.parameters(), lr=1e-7) if args.optimizer == "sgd" else None
+        clip_e = None
+        if args.optimizer == "main_grad_adamw":
+            from tokenpacker_amd import MainGradAdamW
+            m.use_main_grad = True
+            m.init_main_grads()
+            opt = MainGradAdamW(m.parameters(), lr=1e-7, weight_decay=0.0, max_grad_norm=1.0, module=m)
+            opt_e = torch.optim.AdamW(m_eager.parameters(), lr=1e-7, weight_decay=0.0)
+            clip_e = 1.0
 
         def step_hip():
             m.zero_grad(set_to_none=True)
@@ -107,6 +117,8 @@ def main():
         def step_eager():
             m_eager.zero_grad(set_to_none=True)
             (eager_forward(m_eager, x, xm) * w).sum().backward()
+            if clip_e is not None:
+                torch.nn.utils.clip_grad_norm_(m_eager.parameters(), clip_e)
             if opt_e is not None:
                 opt_e.step()
 
@@ -166,6 +178,7 @@ def main():
             continue
         finite = {"hip": all(bool(torch.isfinite(p.float()).all()) for p in m.parameters()),
                   "eager": all(bool(torch.isfinite(p.float()).all()) for p in m_eager.parameters())}
+        m.use_main_grad = False                          # (the agreement check reads .grad)
         m_eager.load_state_dict(m.state_dict())          # gradient agreement on identical weights
         step_eager(); ge = {k: p.grad.float().clone() for k, p in m_eager.named_parameters()}
         m.load_state_dict(m_eager.state_dict()) if False else None
