@@ -41,6 +41,9 @@ extern "C" {
  * the gradients of frozen parameters and can accumulate into fp32 buffers).  Every older entry point keeps its behaviour and its bits. */
 /* ABI 6, extended a third time (by symbol, the version stays 6): tp_optim_tensor, tp_optim_hyper, tp_optim_state,
  * tp_optim_workspace_bytes and tp_optim_step (gradient clipping and AdamW on those fp32 buffers).  Nothing else changes. */
+/* ABI 6, extended a fourth time (by symbol, the version stays 6): tp_desc_known_flags, TP_DESC_RAW_F32 (the raw parameters handed to
+ * tp_pack_weights / tp_backward* may be fp32 master weights, read in place) and tp_optim_hyper.dtype = TP_F32 (AdamW on fp32
+ * parameters that are their own masters).  Without the flag / with a 16-bit optimizer dtype nothing changes, bits included. */
 #define TP_ABI_VERSION 6
 
 typedef enum tp_status {
@@ -69,7 +72,8 @@ typedef struct tp_desc {
     int32_t dtype;         /* tp_dtype of x, x_multi and all weights: TP_BF16 or TP_F16           */
     int32_t out_dtype;     /* tp_dtype of `out`: == dtype, or TP_F32                              */
     float   ln_eps;        /* 1e-6 (builder.py:48)                                                */
-    int32_t flags;         /* 0 | TP_DESC_TRAIN_PACK (tp_pack_weights) | TP_DESC_MASKED (sizes of a masked forward); other bits 0 */
+    int32_t flags;         /* 0 | TP_DESC_TRAIN_PACK (tp_pack_weights) | TP_DESC_MASKED (sizes of a masked forward) |
+                            * TP_DESC_RAW_F32 (tp_pack_weights, tp_backward*); other bits 0 */
     const struct tp_tuning* tuning;    /* ABI 4: the tuning context this call reads its knobs from; NULL: the process-wide table */
 } tp_desc;
 /* tp_pack_weights only: the image will serve tp_forward_train / tp_backward — the weights that only the inference
@@ -80,9 +84,19 @@ typedef struct tp_desc {
  * writes K | V (attention runs in the in-projections' epilogues) and its workspace has no room for them; a masked forward
  * runs the plain schedule, which does — size its workspace with this flag set (tp_forward_masked checks). */
 #define TP_DESC_MASKED 2
+/* tp_pack_weights and every tp_backward* entry point (tp_backward_sink included): EVERY pointer of the tp_weights handed over as
+ * `raw` addresses fp32 elements — the fp32 master weights of a module that runs under autocast — instead of desc.dtype elements;
+ * desc.dtype stays the compute dtype (bf16 / fp16).  Each fp32 element is first rounded to desc.dtype exactly as Tensor.to(dtype)
+ * rounds it (to nearest even, NaN stays NaN, overflow becomes +-inf), on load, inside the kernel that reads it; from there the code
+ * does what it does with a 16-bit source.  The packed image (status word and clamp count included), every dgrad operand and every
+ * gradient are byte-identical to those of 16-bit copies made on the host, and nothing — not the LayerNorm fold, not the fp32
+ * biases — ever reads the unrounded value.  Every pointer must be 16-byte aligned (TP_ERR_INVALID_ARG otherwise: there is no
+ * scalar path).  Other entry points ignore the flag.  A library that predates it answers with its "unknown flags" error; a binding
+ * asks tp_desc_known_flags (detected by symbol). */
+#define TP_DESC_RAW_F32 4
 
-/* The 23 tensors of the reference state dict, all of element type desc.dtype,
- * each contiguous, nn.Linear layout [out_features, in_features]. */
+/* The 23 tensors of the reference state dict, all of element type desc.dtype (all fp32 under
+ * TP_DESC_RAW_F32), each contiguous, nn.Linear layout [out_features, in_features]. */
 typedef struct tp_weights {
     const void* q_proj_1_weight;        /* [1024,1024]  builder.py:59 (no bias)                   */
     const void* k_proj_1_0_weight;      /* [1024,4096]  builder.py:61                             */
@@ -112,6 +126,8 @@ typedef struct tp_weights {
 /* ---- library info ---------------------------------------------------------------------------- */
 int         tp_version(void);                 /* == TP_ABI_VERSION                                 */
 const char* tp_last_error(void);              /* thread-local, never NULL                          */
+/* ABI 6 extension (detected by symbol): the OR of every tp_desc.flags bit this library accepts. */
+int         tp_desc_known_flags(void);
 
 /* ---- sizes ----------------------------------------------------------------------------------- */
 /* Bytes of the packed-weight buffer for (hidden_size, dtype); 0 on invalid arguments. */
@@ -481,8 +497,12 @@ uint32_t tp_backward_plan(uint32_t wanted_params, int want_dx, int want_dx_multi
  *                    lr / weight_decay of its parameter group.  The 16-byte vector path needs all five pointers 16-byte aligned
  *                    and numel % 4 == 0; everything else (element alignment is the minimum) takes a scalar path.
  *   tp_optim_hyper   beta1, beta2 in [0, 1); eps >= 0; max_grad_norm <= 0 or +inf: no clipping (the norm and found_inf are
- *                    computed all the same); dtype TP_BF16 / TP_F16; flags 0 | TP_OPTIM_ZERO_GRAD (grad is zeroed behind the
- *                    update — on a skipped step too).
+ *                    computed all the same); dtype TP_BF16 / TP_F16, or TP_F32; flags 0 | TP_OPTIM_ZERO_GRAD (grad is zeroed
+ *                    behind the update — on a skipped step too).
+ *                    dtype TP_F32: the parameters are fp32 and their own masters (a module that keeps fp32 weights under autocast):
+ *                    every entry's `master` points at the parameter and `param` must be NULL (a non-NULL one is TP_ERR_INVALID_ARG,
+ *                    as a NULL one is for bf16 / fp16).  The update, the skipped step, the zeroing and the vector / scalar paths are
+ *                    the same; there is no second copy and no write-back.
  *   inv_scale        device float (the reciprocal of a loss scale; read by the kernels, never by the host), or NULL: 1.
  *   state            tp_optim_state, a device block of TP_OPTIM_STATE_BYTES the caller zeroes ONCE and keeps across steps:
  *                      grad_norm  the norm of grad * inv_scale before clipping, summed in fp32 per chunk, in fp64 across chunks
@@ -499,7 +519,7 @@ uint32_t tp_backward_plan(uint32_t wanted_params, int want_dx, int want_dx_multi
  *                    the error set on a bad table.
  * TP_ERR_INVALID_ARG before anything is enqueued, the message naming the entry: n < 0, a NULL pointer, numel <= 0, a pointer not
  * aligned to its element size, the same address twice among all pointers of the table, a beta outside [0, 1), negative or
- * non-finite eps / lr / weight_decay, a dtype other than bf16 / fp16, unknown flags, a workspace that is too small.  n == 0 is
+ * non-finite eps / lr / weight_decay, a dtype other than bf16 / fp16 / fp32, unknown flags, a workspace that is too small.  n == 0 is
  * TP_OK and launches nothing. */
 enum { TP_OPTIM_ZERO_GRAD = 1 };
 typedef struct tp_optim_tensor {

@@ -64,6 +64,7 @@ EXPORTED_SYMBOLS = (
     "tp_optim_workspace_bytes", "tp_optim_step",
     "tp_hd_assemble_backward_workspace_bytes", "tp_hd_assemble_backward",
     "tp_splice", "tp_splice_backward_workspace_bytes", "tp_splice_backward",
+    "tp_desc_known_flags",
     "tp_tuning_create", "tp_tuning_destroy", "tp_tuning_set", "tp_tuning_get", "tp_gather_alloc_flags", "tp_gather_free_flags", "tp_gather_export", "tp_gather_open", "tp_gather_close", "tp_gather_push", "tp_gather_sync",
 )
 # include/tokenpacker_test.h: the stateless test hooks — libtokenpacker_exp.so only (load_test_library()), never the product library
@@ -129,8 +130,8 @@ TP_OPTIM_STATE_BYTES = 64
 
 
 class tp_optim_tensor(Structure):
-    """One tensor of tp_optim_step's table: the model-dtype parameter, its fp32 master / gradient / moments, its element count
-    and its parameter group's lr / weight_decay."""
+    """One tensor of tp_optim_step's table: the model-dtype parameter (NULL with dtype TP_F32: the fp32 parameter is the master),
+    its fp32 master / gradient / moments, its element count and its parameter group's lr / weight_decay."""
     _fields_ = [("param", c_void_p), ("master", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p),
                 ("numel", c_int64), ("lr", c_float), ("weight_decay", c_float)]
 
@@ -343,6 +344,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.tp_splice_backward.restype = c_int
     lib.tp_splice_backward.argtypes = [POINTER(tp_splice_args), c_void_p]
 
+    if hasattr(lib, "tp_desc_known_flags"):              # (an ABI 6 extension: an older build lacks it — raw_f32_supported())
+        lib.tp_desc_known_flags.restype = c_int
+        lib.tp_desc_known_flags.argtypes = []
+
     if lib.tp_version() != TP_ABI_VERSION:
         raise TokenPackerLibraryError(
             f"{path}: ABI version {lib.tp_version()} != expected {TP_ABI_VERSION}; rebuild the library")
@@ -421,8 +426,22 @@ def check(rc: int, what: str) -> None:
 
 TP_DESC_TRAIN_PACK = 1
 TP_DESC_MASKED = 2
+TP_DESC_RAW_F32 = 4          # tp_pack_weights / tp_backward*: the tp_weights pointers address fp32 master weights
 TP_IPC_HANDLE_BYTES = 64
 TP_WORKSPACE_STATUS_BYTES = 256
+
+
+_raw_f32 = None
+
+
+def raw_f32_supported() -> bool:
+    """Whether the loaded library reads fp32 master weights in place (``TP_DESC_RAW_F32``; ``tp_optim_step`` on fp32 parameters
+    came with it): the extension is detected by its symbol, ``tp_desc_known_flags``, which an older ABI 6 build lacks."""
+    global _raw_f32
+    if _raw_f32 is None:                                 # (asked on every training step: the answer is kept)
+        lib = load_library()
+        _raw_f32 = hasattr(lib, "tp_desc_known_flags") and bool(lib.tp_desc_known_flags() & TP_DESC_RAW_F32)
+    return _raw_f32
 
 
 def make_desc(batch: int, raw_grid: int, scale_factor: int, hidden_size: int, dtype: int,
@@ -510,5 +529,5 @@ def get_tuning(key: int) -> int:
 
 
 __all__ = [n for n in dir() if n.startswith(("TP_", "tp_"))] + [
-    "load_library", "load_test_library", "last_error", "check", "make_desc", "strides3", "backward_plan", "BWD_STAGE_NAMES", "set_tuning", "get_tuning", "TuningContext",
+    "load_library", "load_test_library", "last_error", "check", "make_desc", "strides3", "backward_plan", "raw_f32_supported", "BWD_STAGE_NAMES", "set_tuning", "get_tuning", "TuningContext",
     "TokenPackerLibraryError", "WEIGHT_FIELDS", "EXPORTED_SYMBOLS", "TEST_SYMBOLS", "LIB_PATH", "EXP_LIB_PATH", "byref"]

@@ -163,7 +163,7 @@ int validate_desc(const tp_desc* d) {
         return TP_ERR_INVALID_ARG;
     }
     if (!(d->ln_eps > 0.f)) { set_error("tp_desc: ln_eps must be > 0"); return TP_ERR_INVALID_ARG; }
-    if (d->flags & ~(TP_DESC_TRAIN_PACK | TP_DESC_MASKED)) { set_error("tp_desc: unknown flags 0x%x", d->flags); return TP_ERR_INVALID_ARG; }
+    if (d->flags & ~tp_desc_known_flags()) { set_error("tp_desc: unknown flags 0x%x", d->flags); return TP_ERR_INVALID_ARG; }
     return TP_OK;
 }
 
@@ -281,6 +281,7 @@ static constexpr int BK_ELEMS = 64;                  // K-slab of the GEMM kerne
 extern "C" {
 
 int tp_version(void) { return TP_ABI_VERSION; }
+int tp_desc_known_flags(void) { return TP_DESC_TRAIN_PACK | TP_DESC_MASKED | TP_DESC_RAW_F32; }
 
 const char* tp_last_error(void) { return g_err; }
 
@@ -362,6 +363,12 @@ int tp_pack_weights(const tp_desc* desc, const tp_weights* raw, void* packed, si
     for (size_t i = 0; i < sizeof(tp_weights) / sizeof(void*); ++i)
         if (!ptrs[i]) { set_error("tp_pack_weights: weight pointer #%zu is NULL", i); return TP_ERR_INVALID_ARG; }
     const int D = desc->hidden_size, dt = desc->dtype;
+    // TP_DESC_RAW_F32: the 23 pointers address fp32 master weights, rounded to `dt` on load by every kernel that reads one
+    const bool raw32 = (desc->flags & TP_DESC_RAW_F32) != 0;
+    const size_t rsz = raw32 ? 4 : 2;                    // bytes per raw element: the offsets into in_proj_weight / in_proj_bias
+    if (raw32)
+        for (size_t i = 0; i < sizeof(tp_weights) / sizeof(void*); ++i)
+            if ((uintptr_t)ptrs[i] & 15) { set_error("tp_pack_weights: fp32 weight pointer #%zu is not 16-byte aligned", i); return TP_ERR_INVALID_ARG; }
     const PackedLayout L = packed_layout(D);
     if (packed_bytes < L.total) {
         set_error("tp_pack_weights: packed buffer %zu B < required %zu B", packed_bytes, L.total);
@@ -394,17 +401,17 @@ int tp_pack_weights(const tp_desc* desc, const tp_weights* raw, void* packed, si
     fits = fits && c16(raw->mlp_0_weight, L.w_m0, (long long)D * E) && c32(raw->mlp_0_bias, (float*)(P + L.b_m0), (long long)D);
     fits = fits && c16(raw->mlp_2_weight, L.w_m2, (long long)D * D) && c32(raw->mlp_2_bias, (float*)(P + L.b_m2), (long long)D);
     if (!fits) { set_error("tp_pack_weights: batch table too small"); return TP_ERR_LAUNCH; }
-    TP_TRY(pack_batch_launch(dt, ops, stream, sat));
+    TP_TRY(pack_batch_launch(dt, ops, stream, sat, raw32));
     // LayerNorm affines folded into the q/k/v in-projections (in_proj rows: q | k | v)
     const char* inw = (const char*)raw->clip_attn_in_proj_weight;
     const char* inb = (const char*)raw->clip_attn_in_proj_bias;
     TP_TRY(pack_ln_fold_launch(dt, inw, inb, raw->ln_q_1_weight, raw->ln_q_1_bias, P + L.w_in_q,
-                               (float*)(P + L.c_in_q), (float*)(P + L.b_in_q), (int)E, (int)E, stream, sat));
-    TP_TRY(pack_ln_fold_launch(dt, inw + E * E * 2, inb + E * 2, raw->ln_k_1_weight, raw->ln_k_1_bias,
-                               P + L.w_in_kv, (float*)(P + L.c_in_kv), (float*)(P + L.b_in_kv), (int)E, (int)E, stream, sat));
-    TP_TRY(pack_ln_fold_launch(dt, inw + 2 * E * E * 2, inb + 2 * E * 2, raw->ln_v_1_weight, raw->ln_v_1_bias,
+                               (float*)(P + L.c_in_q), (float*)(P + L.b_in_q), (int)E, (int)E, stream, sat, raw32));
+    TP_TRY(pack_ln_fold_launch(dt, inw + E * E * rsz, inb + E * rsz, raw->ln_k_1_weight, raw->ln_k_1_bias,
+                               P + L.w_in_kv, (float*)(P + L.c_in_kv), (float*)(P + L.b_in_kv), (int)E, (int)E, stream, sat, raw32));
+    TP_TRY(pack_ln_fold_launch(dt, inw + 2 * E * E * rsz, inb + 2 * E * rsz, raw->ln_v_1_weight, raw->ln_v_1_bias,
                                P + L.w_in_kv + E * E * 2, (float*)(P + L.c_in_kv) + E, (float*)(P + L.b_in_kv) + E,
-                               (int)E, (int)E, stream, sat));
+                               (int)E, (int)E, stream, sat, raw32));
     const bool train_pack = (desc->flags & TP_DESC_TRAIN_PACK) != 0;     // training image: inference-only weights are skipped
     if (!train_pack) TP_TRY(pack_head_transpose_launch(P + L.w_in_kv, P + L.w_qt, stream));      // of the ROUNDED W'k: the absorbed schedule
     // Fused LayerNorm chain of the K/V side (inference, plain schedule; TP_TUNE_FUSE_KV_LN):
@@ -449,8 +456,8 @@ int tp_pack_weights(const tp_desc* desc, const tp_weights* raw, void* packed, si
             TP_TRY(pack_bias_fold_launch(P + L.w_in_kv + (size_t)g * E * E * 2, (const float*)(P + L.b_kv2) + g * E, nullptr,
                                          (float*)(P + L.d_in_kv) + g * E, (int)E, (int)E, stream));
             // the centred chain: Wc' = W'·W2c = (hi + lo)·W2 - c (x) wbar,  d' = W'·b2c = W'·b2 - c mean(b2)   (c = rowsum of the EXACT W')
-            TP_TRY(pack_ln_fold_residual_launch(dt, inw + (size_t)(1 + g) * E * E * 2, gammas[g], (const float*)(P + L.b_kv2) + g * E, lo16,
-                                                c_ex, d_ex, (int)E, (int)E, stream));
+            TP_TRY(pack_ln_fold_residual_launch(dt, inw + (size_t)(1 + g) * E * E * rsz, gammas[g], (const float*)(P + L.b_kv2) + g * E, lo16,
+                                                c_ex, d_ex, (int)E, (int)E, stream, raw32));
             GemmArgs a2 = plain_gemm(lo16, E, P + L.scratch_t, (char*)P2, E, (int)E, (int)E, (int)E, nullptr, 0);
             a2.tile = 128;
             TP_TRY(gemm_launch(TP_F16, TP_F32, a2, stream));
@@ -468,7 +475,7 @@ int tp_pack_weights(const tp_desc* desc, const tp_weights* raw, void* packed, si
             a.tile = 128;
             TP_TRY(gemm_launch(TP_F16, TP_F32, a, stream));
             TP_TRY(pack_round_f16_launch((const float*)(P + L.scratch_p), P + L.w_c_q, (long long)E * E, stream, sat));
-            TP_TRY(pack_ln_fold_residual_launch(dt, inw, gammas[2], nullptr, lo16, c_ex, nullptr, (int)E, (int)E, stream));
+            TP_TRY(pack_ln_fold_residual_launch(dt, inw, gammas[2], nullptr, lo16, c_ex, nullptr, (int)E, (int)E, stream, raw32));
             GemmArgs a2 = plain_gemm(lo16, E, P + L.scratch_t, (char*)P2, E, (int)E, (int)E, (int)E, nullptr, 0);
             a2.tile = 128;
             TP_TRY(gemm_launch(TP_F16, TP_F32, a2, stream));

@@ -103,7 +103,8 @@ static int transpose_launch_t(const void* src, long long ld, int rpb, long long 
 
 // The same 64 x 64 tiling for a BATCH of plain matrices in one launch (round 6: the eight weights the dgrad GEMMs read transposed —
 // 7 us each at a 32-image step, launch latency mostly): blockIdx.z picks the matrix, blocks beyond its tile grid leave at once.
-template <typename TS, typename TD>
+// (TS: the model dtype the sources hold — or, with SRC = float, the dtype the fp32 raw parameters are rounded to on load)
+template <typename TS, typename TD, typename SRC = TS>
 __global__ void __launch_bounds__(256)
 transpose_batch_kernel(const TransposeBatch tb) {
     const TransposeOp o = tb.op[blockIdx.z];
@@ -111,7 +112,7 @@ transpose_batch_kernel(const TransposeBatch tb) {
     __shared__ float tile[64][65];
     using S8 = typename Vec<TS>::x8;
     using D8 = typename Vec<TD>::x8;
-    const TS* __restrict__ src = (const TS*)o.src;
+    const SRC* __restrict__ src = (const SRC*)o.src;
     TD* __restrict__ dst = (TD*)o.dst;
     const int c0 = blockIdx.x * 64, r0 = blockIdx.y * 64;
     const int tr = threadIdx.x >> 2, seg = (threadIdx.x & 3) * 16;
@@ -124,7 +125,7 @@ transpose_batch_kernel(const TransposeBatch tb) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = 0.f;
             if (r < o.R && c < o.C) {
-                const S8 t = *(const S8*)(src + (long long)r * o.ld + c);
+                const S8 t = load_param8<TS>(src + (long long)r * o.ld + c);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] = (float)t[e];
             }
@@ -148,7 +149,7 @@ transpose_batch_kernel(const TransposeBatch tb) {
     }
 }
 
-int bw_transpose_batch_launch(int src_dtype, int dst_dtype, const TransposeBatch& tb, hipStream_t stream) {
+int bw_transpose_batch_launch(int src_dtype, int dst_dtype, const TransposeBatch& tb, hipStream_t stream, bool src_f32) {
     if (tb.count <= 0) return TP_OK;
     if (tb.count > kTransposeBatch) { set_error("bw transpose batch: %d matrices > %d", tb.count, kTransposeBatch); return TP_ERR_INVALID_ARG; }
     int gx = 1, gy = 1;
@@ -161,7 +162,10 @@ int bw_transpose_batch_launch(int src_dtype, int dst_dtype, const TransposeBatch
         gx = std::max(gx, (o.C + 63) / 64); gy = std::max(gy, (o.Rpad + 63) / 64);
     }
     const dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)tb.count);
-#define TP_TRB(SD, DD, TS, TD) if (src_dtype == SD && dst_dtype == DD) { hipLaunchKernelGGL((transpose_batch_kernel<TS, TD>), grid, dim3(256), 0, stream, tb); return check_launch("transpose_batch_kernel"); }
+#define TP_TRB(SD, DD, TS, TD) if (src_dtype == SD && dst_dtype == DD) { \
+        if (src_f32) hipLaunchKernelGGL((transpose_batch_kernel<TS, TD, float>), grid, dim3(256), 0, stream, tb); \
+        else hipLaunchKernelGGL((transpose_batch_kernel<TS, TD>), grid, dim3(256), 0, stream, tb); \
+        return check_launch("transpose_batch_kernel"); }
     TP_TRB(TP_BF16, TP_BF16, bf16_t, bf16_t) TP_TRB(TP_F16, TP_F16, f16_t, f16_t) TP_TRB(TP_BF16, TP_F16, bf16_t, f16_t) TP_TRB(TP_F16, TP_BF16, f16_t, bf16_t)
 #undef TP_TRB
     set_error("bw transpose batch: unsupported dtypes %d -> %d", src_dtype, dst_dtype);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <type_traits>
 #include "../../include/tokenpacker.h"
 
 namespace tp {
@@ -25,6 +26,33 @@ using f32x8_t = float __attribute__((ext_vector_type(8)));
 template <typename T> struct Vec;
 template <> struct Vec<bf16_t> { using x8 = bf16x8; using x4 = bf16x4; };
 template <> struct Vec<f16_t> { using x8 = f16x8; using x4 = f16x4; };
+
+// ---- raw parameters in fp32 (TP_DESC_RAW_F32) -----------------------------------------------------
+// Every kernel that dereferences a tp_weights pointer has an instantiation for fp32 sources next to the model type T: an fp32 master
+// weight is rounded to T on load exactly as Tensor.to(T) rounds it — round to nearest even, overflow to +-inf, NaN stays NaN
+// (bf16: the quiet 0x7FC0; no payload is kept) — so that everything behind the load sees the value a host-side cast would have left
+// in memory.  Nothing reads the unrounded value.
+#if defined(__HIPCC__)
+template <typename T> __device__ __forceinline__ T round_param(float v);
+template <> __device__ __forceinline__ f16_t round_param<f16_t>(float v) { return (f16_t)v; }
+template <> __device__ __forceinline__ bf16_t round_param<bf16_t>(float v) {
+    const uint32_t u = __float_as_uint(v);
+    const uint16_t r = (v != v) ? (uint16_t)0x7FC0u : (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+    return __builtin_bit_cast(bf16_t, r);
+}
+// eight consecutive parameters as T (p 16-byte aligned): one 16-byte load, or two of fp32 — both issued before the first use
+template <typename T, typename S> __device__ __forceinline__ typename Vec<T>::x8 load_param8(const S* p) {
+    if constexpr (std::is_same<S, float>::value) {
+        const f32x4 a = *(const f32x4*)p, b = *((const f32x4*)p + 1);
+        typename Vec<T>::x8 r;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { r[e] = round_param<T>(a[e]); r[4 + e] = round_param<T>(b[e]); }
+        return r;
+    } else {
+        return *(const typename Vec<T>::x8*)p;
+    }
+}
+#endif
 
 // ---- error plumbing ---------------------------------------------------------------------------
 void set_error(const char* fmt, ...);
@@ -234,8 +262,9 @@ int pack_qr_extract_launch(const void* scratch, int m, void* r_f16, float* ctil,
 int pack_center_product_launch(const float* P, const float* c, const float* wbar, void* out_f16, const float* d, float* d_out,
                                hipStream_t stream, int* sat, const float* P2 = nullptr, void* out3_f16 = nullptr);   // out3: rows [hi_0 lo_0 .. hi_15 lo_15]
 // lo = fp16(W' − fp16(W')), c_exact = rowsum(W'), d_exact = W'·v (v may be NULL), W' = w·diag(gamma) exact in fp32 (tp_kernels.hip)
+// (src_f32, here and below: w / gamma / ... are RAW parameters stored in fp32, TP_DESC_RAW_F32 — rounded to `dtype` on load)
 int pack_ln_fold_residual_launch(int dtype, const void* w, const void* gamma, const float* v, void* lo_f16, float* c_exact,
-                                 float* d_exact, int n_out, int n_in, hipStream_t stream);
+                                 float* d_exact, int n_out, int n_in, hipStream_t stream, bool src_f32 = false);
 bool absorb_kv(const tp_desc* desc, bool train);          // whether tp_forward runs the absorbed schedule for desc
 bool fold_out_proj(const tp_desc* desc, bool train);      // whether out_proj is folded into mlp[0] for desc
 int hd_slice_launch(const float* img, int H, int W, int h_block, int w_block, int h_res, int w_res, int hg, int wg,
@@ -263,7 +292,8 @@ struct BatchOps {
         return true;
     }
 };
-int pack_batch_launch(int dtype, const BatchOps& ops, hipStream_t stream, int* sat);
+// (src_f32: every source is fp32, 16-byte aligned with n % 8 == 0 — anything else is TP_ERR_INVALID_ARG, there is no scalar path)
+int pack_batch_launch(int dtype, const BatchOps& ops, hipStream_t stream, int* sat, bool src_f32 = false);
 // `sat` (optional): device int incremented once per element that did not fit fp16 and was clamped to +-65504
 int pack_cast_f16_launch(int dtype, const void* src, void* dst_f16, long long n, hipStream_t stream, int* sat = nullptr);
 int pack_transpose_f16_launch(const void* src_f16, void* dst_f16, int n, hipStream_t stream);          // [n,n]
@@ -272,7 +302,7 @@ int pack_bias_fold_launch(const void* w_f16, const float* v, const float* b, flo
                           hipStream_t stream);                                             // out = w·v + b  (b may be NULL)
 int pack_ln_fold_launch(int dtype, const void* w, const void* bias, const void* gamma,
                         const void* beta, void* w_out, float* colsum, float* bias_out, int n_out,
-                        int n_in, hipStream_t stream, int* sat = nullptr);
+                        int n_in, hipStream_t stream, int* sat = nullptr, bool src_f32 = false);
 // debug: counts[i] += number of fp16 elements of buf[i] (n[i] of them) with |v| >= 65504 or NaN (a saturated epilogue)
 int count_saturated_launch(const void* buf, long long n, int* count, hipStream_t stream);
 
@@ -369,7 +399,8 @@ struct TransposeBatch {
         return true;
     }
 };
-int bw_transpose_batch_launch(int src_dtype, int dst_dtype, const TransposeBatch& tb, hipStream_t stream);
+// (src_f32: the sources are fp32 raw parameters, rounded to src_dtype on load)
+int bw_transpose_batch_launch(int src_dtype, int dst_dtype, const TransposeBatch& tb, hipStream_t stream, bool src_f32 = false);
 int bw_reduce_parts_launch(int dst_dtype, const float* part, long long part_stride, int nparts, long long n, void* out,
                            hipStream_t stream, const float* out_scale = nullptr, bool accumulate = false);
 // Dynamic power-of-two scale of a gradient tensor (the backward of a bf16 model runs its chain in fp16 — 11-bit mantissas, the

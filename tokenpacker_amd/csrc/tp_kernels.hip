@@ -945,13 +945,52 @@ pack_batch_kernel(const BatchOps ops, int* __restrict__ sat) {
     }
 }
 
-int pack_batch_launch(int dtype, const BatchOps& ops, hipStream_t stream, int* sat) {
+// The same batch with fp32 raw parameters as sources (TP_DESC_RAW_F32): eight elements arrive in two 16-byte loads, are rounded to
+// the model type T as Tensor.to(T) rounds them (load_param8) and then take pack_batch_kernel's own conversions, so the destination
+// holds the bytes that kernel writes from a 16-bit copy.  The launch refuses what cannot be read this way: there is no scalar path.
+// (A kernel of its own: the 16-bit kernel keeps its instructions.)
+template <typename T>
+__global__ void __launch_bounds__(256)
+pack_batch_f32_kernel(const BatchOps ops, int* __restrict__ sat) {
+    const BatchOp o = ops.op[blockIdx.y];
+    using S8 = typename Vec<T>::x8;
+    const long long stride = (long long)gridDim.x * blockDim.x, t0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    for (long long i = t0; i < o.n / 8; i += stride) {
+        const S8 v = load_param8<T>((const float*)o.src + 8 * i);
+        if (o.kind == BATCH_OP_COPY16) { *((S8*)o.dst + i) = v; }
+        else if (o.kind == BATCH_OP_TO_F32) {
+            f32x4 a, b;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { a[e] = (float)v[e]; b[e] = (float)v[4 + e]; }
+            *((f32x4*)o.dst + 2 * i) = a; *((f32x4*)o.dst + 2 * i + 1) = b;
+        } else {
+            f16x8 r;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) r[e] = (f16_t)clamp_f16_range((float)v[e], sat);
+            *((f16x8*)o.dst + i) = r;
+        }
+    }
+}
+
+int pack_batch_launch(int dtype, const BatchOps& ops, hipStream_t stream, int* sat, bool src_f32) {
     if (ops.count <= 0) return TP_OK;
     if (ops.count > kBatchOps) { set_error("pack batch: %d operations > %d", ops.count, kBatchOps); return TP_ERR_INVALID_ARG; }
     long long nmax = 0;
     for (int i = 0; i < ops.count; ++i) nmax = ops.op[i].n > nmax ? ops.op[i].n : nmax;
     long long bx = (nmax / 8 + 255) / 256;
     bx = bx < 1 ? 1 : (bx > 1024 ? 1024 : bx);
+    if (src_f32) {
+        for (int i = 0; i < ops.count; ++i)
+            if ((ops.op[i].n & 7) || (((uintptr_t)ops.op[i].src | (uintptr_t)ops.op[i].dst) & 15)) {
+                set_error("pack batch: fp32 source #%d is not 16-byte aligned with a multiple of 8 elements", i);
+                return TP_ERR_INVALID_ARG;
+            }
+        if (dtype == TP_BF16)
+            hipLaunchKernelGGL(pack_batch_f32_kernel<bf16_t>, dim3((unsigned)bx, (unsigned)ops.count), dim3(256), 0, stream, ops, sat);
+        else
+            hipLaunchKernelGGL(pack_batch_f32_kernel<f16_t>, dim3((unsigned)bx, (unsigned)ops.count), dim3(256), 0, stream, ops, sat);
+        return check_launch("pack_batch_f32_kernel");
+    }
     if (dtype == TP_BF16)
         hipLaunchKernelGGL(pack_batch_kernel<bf16_t>, dim3((unsigned)bx, (unsigned)ops.count), dim3(256), 0, stream, ops, sat);
     else
@@ -1091,8 +1130,98 @@ pack_ln_fold_residual_kernel(const T* __restrict__ w, const T* __restrict__ gamm
     }
 }
 
+// The two LayerNorm-fold kernels with fp32 raw parameters as sources (TP_DESC_RAW_F32).  The row of W and the affines arrive in
+// 16-byte loads, all issued before the first use, are rounded to the model type T as Tensor.to(T) rounds them and laid into LDS;
+// the loops then are those of the 16-bit kernels, reading LDS — lane t keeps elements t, t + 256, ...: the per-lane order of the
+// sums is part of the image's bits.  n_in <= kEmbed, a multiple of 4 (the launches check).  (Kernels of their own: the 16-bit
+// kernels keep their instructions.)
+template <typename T>
+__device__ __forceinline__ void stage_params(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ c,
+                                             T* sa, T* sb, T* sc, int n) {
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    for (int k = threadIdx.x * 4; k < n; k += blockDim.x * 4) {
+        const f32x4 va = *(const f32x4*)(a + k), vb = *(const f32x4*)(b + k), vc = c ? *(const f32x4*)(c + k) : zero4;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            sa[k + e] = round_param<T>(va[e]);
+            sb[k + e] = round_param<T>(vb[e]);
+            if (c) sc[k + e] = round_param<T>(vc[e]);
+        }
+    }
+    __syncthreads();
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+pack_ln_fold_f32_kernel(const float* __restrict__ w, const float* __restrict__ bias, const float* __restrict__ gamma,
+                        const float* __restrict__ beta, f16_t* __restrict__ w_out, float* __restrict__ colsum,
+                        float* __restrict__ bias_out, int n_in, int* sat) {
+    __shared__ T sw[kEmbed], sg[kEmbed], sb[kEmbed];
+    const int n = blockIdx.x;
+    stage_params<T>(w + (long long)n * n_in, gamma, beta, sw, sg, sb, n_in);
+    float cs = 0.f, bs = 0.f;
+    for (int kk = threadIdx.x; kk < n_in; kk += blockDim.x) {
+        const float wv = (float)sw[kk];
+        const f16_t wp = (f16_t)clamp_f16_range(wv * (float)sg[kk], sat);
+        w_out[(long long)n * n_in + kk] = wp;
+        cs += (float)wp;
+        bs = fmaf((float)sb[kk], wv, bs);
+    }
+    __shared__ float red[2][4];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) { cs += __shfl_xor(cs, off); bs += __shfl_xor(bs, off); }
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = cs; red[1][threadIdx.x >> 6] = bs; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        colsum[n] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+        bias_out[n] = red[1][0] + red[1][1] + red[1][2] + red[1][3] + (float)round_param<T>(bias[n]);
+    }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+pack_ln_fold_residual_f32_kernel(const float* __restrict__ w, const float* __restrict__ gamma, const float* __restrict__ v,
+                                 f16_t* __restrict__ lo, float* __restrict__ c_exact, float* __restrict__ d_exact, int n_in) {
+    __shared__ T sw[kEmbed], sg[kEmbed];
+    const int n = blockIdx.x;
+    stage_params<T>(w + (long long)n * n_in, gamma, nullptr, sw, sg, nullptr, n_in);
+    float cs = 0.f, ds = 0.f;
+    for (int kk = threadIdx.x; kk < n_in; kk += blockDim.x) {
+        const float we = (float)sw[kk] * (float)sg[kk];
+        const float hi = (float)(f16_t)fminf(fmaxf(we, -65504.f), 65504.f);
+        lo[(long long)n * n_in + kk] = (f16_t)(we - hi);
+        cs += we;
+        if (v) ds = fmaf(we, v[kk], ds);
+    }
+    __shared__ float red[2][4];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) { cs += __shfl_xor(cs, off); ds += __shfl_xor(ds, off); }
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = cs; red[1][threadIdx.x >> 6] = ds; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        c_exact[n] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+        if (d_exact) d_exact[n] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+    }
+}
+
+static bool ln_fold_f32_readable(const char* what, int n_in, const void* a, const void* b, const void* c) {
+    if (n_in <= kEmbed && (n_in & 3) == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0) return true;
+    set_error("%s: fp32 sources must be 16-byte aligned and n_in = %d a multiple of 4, at most %d", what, n_in, kEmbed);
+    return false;
+}
+
 int pack_ln_fold_residual_launch(int dtype, const void* w, const void* gamma, const float* v, void* lo_f16, float* c_exact,
-                                 float* d_exact, int n_out, int n_in, hipStream_t stream) {
+                                 float* d_exact, int n_out, int n_in, hipStream_t stream, bool src_f32) {
+    if (src_f32) {
+        if (!ln_fold_f32_readable("pack_ln_fold_residual", n_in, w, gamma, nullptr)) return TP_ERR_INVALID_ARG;
+        if (dtype == TP_BF16)
+            hipLaunchKernelGGL(pack_ln_fold_residual_f32_kernel<bf16_t>, dim3(n_out), dim3(256), 0, stream, (const float*)w,
+                               (const float*)gamma, v, (f16_t*)lo_f16, c_exact, d_exact, n_in);
+        else
+            hipLaunchKernelGGL(pack_ln_fold_residual_f32_kernel<f16_t>, dim3(n_out), dim3(256), 0, stream, (const float*)w,
+                               (const float*)gamma, v, (f16_t*)lo_f16, c_exact, d_exact, n_in);
+        return check_launch("pack_ln_fold_residual_f32_kernel");
+    }
     if (dtype == TP_BF16)
         hipLaunchKernelGGL(pack_ln_fold_residual_kernel<bf16_t>, dim3(n_out), dim3(256), 0, stream, (const bf16_t*)w,
                            (const bf16_t*)gamma, v, (f16_t*)lo_f16, c_exact, d_exact, n_in);
@@ -1104,7 +1233,20 @@ int pack_ln_fold_residual_launch(int dtype, const void* w, const void* gamma, co
 
 int pack_ln_fold_launch(int dtype, const void* w, const void* bias, const void* gamma,
                         const void* beta, void* w_out, float* colsum, float* bias_out, int n_out,
-                        int n_in, hipStream_t stream, int* sat) {
+                        int n_in, hipStream_t stream, int* sat, bool src_f32) {
+    if (src_f32) {
+        if (!ln_fold_f32_readable("pack_ln_fold", n_in, w, gamma, beta) || ((uintptr_t)bias & 3)) {
+            if (((uintptr_t)bias & 3)) set_error("pack_ln_fold: fp32 bias is not 4-byte aligned");
+            return TP_ERR_INVALID_ARG;
+        }
+        if (dtype == TP_BF16)
+            hipLaunchKernelGGL(pack_ln_fold_f32_kernel<bf16_t>, dim3(n_out), dim3(256), 0, stream, (const float*)w, (const float*)bias,
+                               (const float*)gamma, (const float*)beta, (f16_t*)w_out, colsum, bias_out, n_in, sat);
+        else
+            hipLaunchKernelGGL(pack_ln_fold_f32_kernel<f16_t>, dim3(n_out), dim3(256), 0, stream, (const float*)w, (const float*)bias,
+                               (const float*)gamma, (const float*)beta, (f16_t*)w_out, colsum, bias_out, n_in, sat);
+        return check_launch("pack_ln_fold_f32_kernel");
+    }
     if (dtype == TP_BF16)
         hipLaunchKernelGGL(pack_ln_fold_kernel<bf16_t>, dim3(n_out), dim3(256), 0, stream,
                            (const bf16_t*)w, (const bf16_t*)bias, (const bf16_t*)gamma, (const bf16_t*)beta,

@@ -4,6 +4,7 @@
 //   optim_prepare_kernel  one workgroup: the partials summed in index order in fp64 -> the state block (norm, coefficient,
 //                         found_inf, the step counters, the bias corrections of the step being applied)
 //   optim_adamw_kernel    one workgroup per chunk: the AdamW update on the fp32 masters, the model-dtype write-back, the zeroing
+//                         (T = float: the fp32 parameter IS the master — no write-back, `param` is NULL)
 // A chunk is a fixed number of elements and every sum has a fixed order (a serial chain of kOptimChain terms per lane, then a
 // fixed tree over the workgroup; the partials in index order): results do not depend on the grid or on the number of CUs, and two
 // runs give the same bits.  The table travels by value as a kernel argument (pack_batch_kernel's style); a longer list is
@@ -156,7 +157,8 @@ template <typename T>
 __global__ void __launch_bounds__(kOptimThreads)
 optim_adamw_kernel(const OptimTable tab, const float* __restrict__ inv_scale, const tp_optim_state* __restrict__ st, float beta1,
                    float beta2, float eps, unsigned flags) {
-    using T4 = typename Vec<T>::x4;
+    constexpr bool kWriteBack = !std::is_same<T, float>::value;    // fp32 parameters are their own masters: nothing to write back
+    using T4 = typename std::conditional<kWriteBack, Vec<T>, Vec<f16_t>>::type::x4;
     const int c = tab.chunk_base + (int)blockIdx.x;
     const OptimEntry e = tab.e[optim_entry_of(tab, c)];
     const long long base = (long long)(c - e.first_chunk) * kOptimChunk;
@@ -169,9 +171,10 @@ optim_adamw_kernel(const OptimTable tab, const float* __restrict__ inv_scale, co
     float* pm = e.master + base;
     float* m = e.exp_avg + base;
     float* v = e.exp_avg_sq + base;
-    T* pp = (T*)e.param + base;
+    T* pp = kWriteBack ? (T*)e.param + base : nullptr;
     const bool vec = (e.numel & 3) == 0 &&
                      (((uintptr_t)e.grad | (uintptr_t)e.master | (uintptr_t)e.exp_avg | (uintptr_t)e.exp_avg_sq | (uintptr_t)e.param) & 15) == 0;
+    // (T = float: e.param is NULL — it adds nothing to the alignment test, and pp is never dereferenced)
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     if (skip) {                                        // a skipped step: master, exp_avg, exp_avg_sq and param keep their bits
         if (vec) {
@@ -222,12 +225,12 @@ optim_adamw_kernel(const OptimTable tab, const float* __restrict__ inv_scale, co
                 float p_ = pv[j][q], m_ = mv[j][q], v_ = vv[j][q];
                 adamw_update(k, gv[j][q], p_, m_, v_);
                 pv[j][q] = p_; mv[j][q] = m_; vv[j][q] = v_;
-                out[q] = (T)p_;                         // round to nearest even, no clamp (Tensor.to)
+                if constexpr (kWriteBack) out[q] = (T)p_;   // round to nearest even, no clamp (Tensor.to)
             }
             *((f32x4*)m + i) = mv[j];
             *((f32x4*)v + i) = vv[j];
             *((f32x4*)pm + i) = pv[j];
-            *((T4*)pp + i) = out;
+            if constexpr (kWriteBack) *((T4*)pp + i) = out;
             if (zero) *((f32x4*)g + i) = zero4;
         }
     } else {
@@ -249,7 +252,7 @@ optim_adamw_kernel(const OptimTable tab, const float* __restrict__ inv_scale, co
             m[i] = mv[j];
             v[i] = vv[j];
             pm[i] = pv[j];
-            pp[i] = (T)pv[j];
+            if constexpr (kWriteBack) pp[i] = (T)pv[j];
             if (zero) g[i] = 0.f;
         }
     }
@@ -295,14 +298,22 @@ int tp_optim_step(const tp_optim_tensor* t, int n, const tp_optim_hyper* h, cons
     if (!(h->beta2 >= 0.f && h->beta2 < 1.f)) { set_error("%s: beta2 = %g outside [0, 1)", what, (double)h->beta2); return TP_ERR_INVALID_ARG; }
     if (!finite_nonneg(h->eps)) { set_error("%s: eps = %g must be finite and >= 0", what, (double)h->eps); return TP_ERR_INVALID_ARG; }
     if (h->max_grad_norm != h->max_grad_norm) { set_error("%s: max_grad_norm is NaN (<= 0 or +inf: no clipping)", what); return TP_ERR_INVALID_ARG; }
-    if (h->dtype != TP_BF16 && h->dtype != TP_F16) { set_error("%s: dtype %d unsupported (the parameters are bf16 / fp16)", what, h->dtype); return TP_ERR_INVALID_ARG; }
+    if (h->dtype != TP_BF16 && h->dtype != TP_F16 && h->dtype != TP_F32) {
+        set_error("%s: dtype %d unsupported (the parameters are bf16 / fp16, or fp32 and their own masters)", what, h->dtype);
+        return TP_ERR_INVALID_ARG;
+    }
+    const bool own_master = h->dtype == TP_F32;          // `master` is the fp32 parameter itself; `param` must be NULL
     if (h->flags & ~(uint32_t)TP_OPTIM_ZERO_GRAD) { set_error("%s: unknown flags 0x%x", what, h->flags); return TP_ERR_INVALID_ARG; }
     std::vector<std::pair<uintptr_t, int>> seen;
     seen.reserve((size_t)n * 5);
     for (int i = 0; i < n; ++i) {
         const void* ptr[5] = {t[i].param, t[i].master, t[i].grad, t[i].exp_avg, t[i].exp_avg_sq};
         static const char* const name[5] = {"param", "master", "grad", "exp_avg", "exp_avg_sq"};
-        for (int k = 0; k < 5; ++k) {
+        if (own_master && ptr[0]) {
+            set_error("%s: entry #%d: param must be NULL with dtype TP_F32 (master is the parameter)", what, i);
+            return TP_ERR_INVALID_ARG;
+        }
+        for (int k = own_master ? 1 : 0; k < 5; ++k) {
             if (!ptr[k]) { set_error("%s: entry #%d: %s is NULL", what, i, name[k]); return TP_ERR_INVALID_ARG; }
             if ((uintptr_t)ptr[k] & (k == 0 ? 1 : 3)) {
                 set_error("%s: entry #%d: %s is not aligned to its %d-byte elements", what, i, name[k], k == 0 ? 2 : 4);
@@ -353,6 +364,10 @@ int tp_optim_step(const tp_optim_tensor* t, int n, const tp_optim_hyper* h, cons
                 if (int rc = check_launch("optim_sumsq_kernel")) return rc;
             } else if (h->dtype == TP_BF16) {
                 hipLaunchKernelGGL(optim_adamw_kernel<bf16_t>, grid, block, 0, stream, tab, inv_scale, (const tp_optim_state*)st, h->beta1,
+                                   h->beta2, h->eps, (unsigned)h->flags);
+                if (int rc = check_launch("optim_adamw_kernel")) return rc;
+            } else if (h->dtype == TP_F32) {
+                hipLaunchKernelGGL(optim_adamw_kernel<float>, grid, block, 0, stream, tab, inv_scale, (const tp_optim_state*)st, h->beta1,
                                    h->beta2, h->eps, (unsigned)h->flags);
                 if (int rc = check_launch("optim_adamw_kernel")) return rc;
             } else {

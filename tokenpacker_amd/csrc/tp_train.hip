@@ -350,6 +350,14 @@ static int backward_impl(const tp_desc* desc, const void* x_multi, const void* c
             if (sink && gp[i]) wanted |= pbit((int)i);
         }
     }
+    // TP_DESC_RAW_F32: `raw` addresses fp32 master weights; every kernel below that reads one rounds it to the model dtype on load
+    const bool raw32 = (desc->flags & TP_DESC_RAW_F32) != 0;
+    const size_t rsz = raw32 ? 4 : 2;                    // bytes per raw element: the offsets into in_proj_weight
+    if (raw32) {
+        const void* const* wp = reinterpret_cast<const void* const*>(raw);
+        for (size_t i = 0; i < P_COUNT; ++i)
+            if ((uintptr_t)wp[i] & 15) { set_error("tp_backward: fp32 weight pointer #%zu is not 16-byte aligned", i); return TP_ERR_INVALID_ARG; }
+    }
     // the sink: element type of its entries (the model dtype, or fp32 — then they may accumulate)
     const int OT = sink ? sink->dtype : desc->dtype;
     const bool acc = sink && sink->accumulate != 0;
@@ -506,10 +514,10 @@ static int backward_impl(const tp_desc* desc, const void* x_multi, const void* c
         bool ok = tb.add(raw->mlp_2_weight, D, D, D, bw + L.wt_m2, D) && tb.add(raw->mlp_0_weight, E, D, E, bw + L.wt_m0, D) &&
                   tb.add(raw->clip_attn_out_proj_weight, E, E, E, bw + L.wt_out, E);
         for (int t = 0; t < 3; ++t)
-            ok = ok && tb.add((const char*)raw->clip_attn_in_proj_weight + (size_t)t * E * E * 2, E, E, E, bw + L.wt_in + (size_t)t * E * E * 2, E);
+            ok = ok && tb.add((const char*)raw->clip_attn_in_proj_weight + (size_t)t * E * E * rsz, E, E, E, bw + L.wt_in + (size_t)t * E * E * 2, E);
         ok = ok && tb.add(raw->k_proj_1_2_weight, E, E, E, bw + L.wt_2, E) && tb.add(raw->v_proj_1_2_weight, E, E, E, bw + L.wt_2 + (size_t)E * E * 2, E);
         if (!ok) { set_error("tp_backward: transpose batch table too small"); return TP_ERR_LAUNCH; }
-        TP_TRY(bw_transpose_batch_launch(MT, GT, tb, stream));
+        TP_TRY(bw_transpose_batch_launch(MT, GT, tb, stream, raw32));
     }
     float* ln_g = (float*)(bw + L.ln_g);
     float* ln_b = (float*)(bw + L.ln_b);
@@ -518,7 +526,7 @@ static int backward_impl(const tp_desc* desc, const void* x_multi, const void* c
     {
         BatchOps ops{};                                  // (six 1 K-element casts: one launch)
         for (int t = 0; t < 3; ++t) { ops.add(BATCH_OP_TO_F32, gam_src[t], ln_g + t * E, E); ops.add(BATCH_OP_TO_F32, bet_src[t], ln_b + t * E, E); }
-        TP_TRY(pack_batch_launch(MT, ops, stream, nullptr));
+        TP_TRY(pack_batch_launch(MT, ops, stream, nullptr, raw32));
     }
 
     // ---- the incoming gradient: as it is, or (fp16 chain) scaled by a dynamic power of two and cast ----------------------
@@ -700,10 +708,10 @@ static int backward_impl(const tp_desc* desc, const void* x_multi, const void* c
         TransposeBatch tb{};                             // [Wk0; Wv0]^T [4096, 2E] in the model dtype: dZ1 left the chain in it
         tb.op[tb.count++] = TransposeOp{raw->k_proj_1_0_weight, bw + L.wt_kv0, kMulti, 2 * E, E, kMulti, E, 0};
         tb.op[tb.count++] = TransposeOp{raw->v_proj_1_0_weight, bw + L.wt_kv0 + (size_t)E * 2, kMulti, 2 * E, E, kMulti, E, 0};
-        if (want_dxm) TP_TRY(bw_transpose_batch_launch(MT, MT, tb, stream));
+        if (want_dxm) TP_TRY(bw_transpose_batch_launch(MT, MT, tb, stream, raw32));
         TransposeBatch tq{};                             // Wq1^T [E, E] in the gradient dtype (dQ1pre's)
         tq.add(raw->q_proj_1_weight, E, E, E, bw + L.wt_q1, E);
-        if (dx) TP_TRY(bw_transpose_batch_launch(MT, GT, tq, stream));
+        if (dx) TP_TRY(bw_transpose_batch_launch(MT, GT, tq, stream, raw32));
     }
     if (want_dxm) {
         // dx_multi [R, 4096] = dZ1 [R, 2E] · [Wk0; Wv0], times 1 / S in the epilogue, rounded once to the model dtype.  The

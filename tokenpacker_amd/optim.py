@@ -4,7 +4,8 @@ The consumer of ``module.use_main_grad``: with it every backward ADDS unrounded 
 autograd ``None``, so ``p.grad`` stays ``None`` and no stock optimizer sees a gradient.  This optimizer reads those buffers:
 the global L2 norm (``clip_grad_norm_``'s formula, HF's ``max_grad_norm``), ``torch.optim.AdamW``'s update (the reference's
 ``optim = "adamw_torch"``, train.py:81) on fp32 master weights, the write-back into the bf16 / fp16 parameters and the zeroing of
-``main_grad`` — three launches on the current stream, no host synchronisation, bit-reproducible.  A non-finite gradient norm skips
+``main_grad`` — three launches on the current stream, no host synchronisation, bit-reproducible.  fp32 parameters (an fp32 module
+that runs under ``torch.autocast``) are their own masters: the update is applied to them in place, with no copy and no write-back.  A non-finite gradient norm skips
 the step on the device and is counted (``found_inf``, ``steps_skipped``).
 
 It is a ``torch.optim.Optimizer``: parameter groups with their own ``lr`` / ``weight_decay`` (what
@@ -21,7 +22,7 @@ import torch
 from . import _capi
 from .projector import checked_main_grad
 
-_DTYPES = {torch.bfloat16: _capi.TP_BF16, torch.float16: _capi.TP_F16}
+_DTYPES = {torch.bfloat16: _capi.TP_BF16, torch.float16: _capi.TP_F16, torch.float32: _capi.TP_F32}
 # words of the device state block (tp_optim_state, include/tokenpacker.h)
 _W_NORM, _W_COEF, _W_FOUND_INF, _W_STEP, _W_SKIPPED = 0, 1, 2, 3, 4
 _STATE_WORDS = _capi.TP_OPTIM_STATE_BYTES // 4
@@ -37,7 +38,8 @@ class MainGradAdamW(torch.optim.Optimizer):
     ``module``: a ``TokenPacker`` whose weight image is dropped after every step (``invalidate_packed()``: the step writes
     ``p.data`` through raw pointers, without a version bump); also names the parameters in error messages.
 
-    Master weights start as ``p.detach().float()``.  ``grad_norm``, ``clip_coef``, ``found_inf``, ``steps_applied`` and
+    Master weights start as ``p.detach().float()``; for fp32 parameters ``state[p]["master"]`` is ``p.data`` itself (12 bytes of
+    state per element less, and ``state_dict()`` carries no ``master``: the module's own state dict has it).  ``grad_norm``, ``clip_coef``, ``found_inf``, ``steps_applied`` and
     ``steps_skipped`` are views of the device state block: reading them (``.item()``) is the caller's synchronisation."""
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
@@ -67,27 +69,31 @@ class MainGradAdamW(torch.optim.Optimizer):
                     continue
                 checked_main_grad(name, p)           # (the named TypeError / ValueError comes first, as in the module)
                 self._entries.append((group, p, name))
-        for _, p, name in self._entries:
-            if not p.is_cuda:
-                raise RuntimeError("tokenpacker_amd.optim.MainGradAdamW runs only on an AMD GPU (HIP kernels); there is no CPU fallback")
+        first = self._entries[0][1] if self._entries else None
+        for _, p, name in self._entries:                    # (what the parameters ARE before where they are: named on any device)
             if p.dtype not in _DTYPES:
                 raise TypeError(f"MainGradAdamW: parameter {name} is {p.dtype}; the parameters are torch.bfloat16 or torch.float16 "
-                                f"(their fp32 masters live in the optimizer)")
-        first = self._entries[0][1] if self._entries else None
-        for _, p, name in self._entries:
+                                f"(their fp32 masters live in the optimizer), or torch.float32 (their own masters)")
             if p.dtype != first.dtype or p.device != first.device:
                 raise ValueError(f"MainGradAdamW: parameter {name} is {p.dtype} on {p.device}, the first one {first.dtype} on "
                                  f"{first.device}: one dtype and one device per optimizer")
             if not p.is_contiguous():
                 raise ValueError(f"MainGradAdamW: parameter {name} must be contiguous")
+        for _, p, name in self._entries:
+            if not p.is_cuda:
+                raise RuntimeError("tokenpacker_amd.optim.MainGradAdamW runs only on an AMD GPU (HIP kernels); there is no CPU fallback")
         self._device = first.device if first is not None else None
         self._dtype = first.dtype if first is not None else None
+        self._own_master = self._dtype == torch.float32      # fp32 parameters: updated in place, tp_optim_tensor.param stays NULL
+        if self._own_master and not _capi.raw_f32_supported():
+            raise RuntimeError("MainGradAdamW: fp32 parameters need a library with the TP_F32 optimizer mode (tp_desc_known_flags); "
+                               "rebuild libtokenpacker_hip.so")
         n = len(self._entries)
         self._table = (_capi.tp_optim_tensor * max(n, 1))()
         for i, (_, p, _name) in enumerate(self._entries):
             st = self.state[p]
             st["step"] = torch.tensor(0.0)
-            st["master"] = p.detach().float().contiguous()
+            st["master"] = p.data if self._own_master else p.detach().float().contiguous()
             st["exp_avg"] = torch.zeros(p.shape, dtype=torch.float32, device=p.device)
             st["exp_avg_sq"] = torch.zeros(p.shape, dtype=torch.float32, device=p.device)
             e = self._table[i]
@@ -143,7 +149,7 @@ class MainGradAdamW(torch.optim.Optimizer):
 
     # ---- the step -----------------------------------------------------------------------------------------------------------
     def step(self, closure=None, inv_scale: Optional[torch.Tensor] = None):
-        """Clip + AdamW + write-back (+ zeroing) on the current stream; returns without synchronising.  ``inv_scale``: a one-element
+        """Clip + AdamW + write-back (none for fp32 parameters) (+ zeroing) on the current stream; returns without synchronising.  ``inv_scale``: a one-element
         fp32 device tensor the gradients are multiplied by (the reciprocal of a loss scale), or None."""
         loss = None
         if closure is not None:
@@ -161,11 +167,15 @@ class MainGradAdamW(torch.optim.Optimizer):
             ptr = mg.data_ptr() if isinstance(mg, torch.Tensor) else None
             if ptr is None or ptr != e.grad:
                 e.grad = checked_main_grad(name, p).data_ptr()     # (a new buffer: held to the contract before its address is used)
-            if p.data_ptr() != e.param:
+            if p.data_ptr() != (e.master if self._own_master else e.param):
                 if p.dtype != self._dtype or p.device != self._device or not p.is_contiguous() or p.numel() != e.numel:
                     raise RuntimeError(f"MainGradAdamW: parameter {name} changed its dtype, device, size or layout after the "
                                        f"optimizer was built")
-                e.param = p.data_ptr()
+                if self._own_master:             # (p.data was replaced: the master follows the parameter)
+                    self.state[p]["master"] = p.data
+                    e.master = p.data_ptr()
+                else:
+                    e.param = p.data_ptr()
             e.lr, e.weight_decay = group["lr"], group["weight_decay"]
         inv_ptr = None
         if inv_scale is not None:
@@ -190,14 +200,15 @@ class MainGradAdamW(torch.optim.Optimizer):
 
     def state_dict(self):
         """torch's layout (``state`` by parameter index with ``step`` / ``exp_avg`` / ``exp_avg_sq``, ``param_groups`` with torch's
-        keys) plus ``master`` per parameter and the device counters under ``main_grad_adamw``.  Reads the counters: synchronises."""
+        keys) plus ``master`` per bf16 / fp16 parameter and the device counters under ``main_grad_adamw``.  Reads the counters: synchronises."""
         applied, skipped = (0, 0) if self._block is None else (int(v) for v in self._block[_W_STEP:_W_SKIPPED + 1].tolist())
         index = {id(p): i for i, p in enumerate(self._indexed_params())}
         state = {}
         for _, p, _name in self._entries:
             st = self.state[p]
-            state[index[id(p)]] = {"step": torch.tensor(float(applied)), "exp_avg": st["exp_avg"], "exp_avg_sq": st["exp_avg_sq"],
-                                   "master": st["master"]}
+            state[index[id(p)]] = {"step": torch.tensor(float(applied)), "exp_avg": st["exp_avg"], "exp_avg_sq": st["exp_avg_sq"]}
+            if not self._own_master:
+                state[index[id(p)]]["master"] = st["master"]
         groups, start = [], 0
         for group in self.param_groups:
             packed = {k: v for k, v in group.items() if k != "params"}

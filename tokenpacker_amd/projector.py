@@ -161,11 +161,19 @@ class TokenPacker(nn.Module):
         #: dtype to compute in (torch.float16 / torch.bfloat16): operands are rounded to it, the result comes back
         #: as fp32 from the last GEMM's accumulators (within 1e-3 of the fp32 reference, not bit-comparable to it).
         self.fp32_compute_dtype: Optional[torch.dtype] = None
+        #: fp32 master weights are read IN PLACE: when all 23 parameters are fp32, contiguous, 16-byte aligned and on the device
+        #: (an fp32 module under autocast, or with ``fp32_compute_dtype``), the pack and the backward hand the parameters' own
+        #: pointers to the library (``TP_DESC_RAW_F32``), whose kernels round each element to the compute dtype on load — the
+        #: bytes ``Tensor.to(dtype)`` would have written, so every result is byte-identical, without the 2 x 23 casts and the
+        #: two 16-bit copies of the weights per training step.  Set True to force the host-side casts instead (A/B runs, tests);
+        #: mixed-dtype modules and libraries without the extension take them anyway.  ``last_pack_path`` says which ran.
+        self.host_cast_weights = False
         #: a ``_capi.TuningContext`` this module's calls read their knobs from (``tp_desc.tuning``): a serving worker that runs
         #: several model instances / threads gives each its own, and nobody's ``set_tuning`` can change another's schedule or
         #: low bits.  None (default): the library's process-wide table.  Not copied by deepcopy / pickle.
         self.tuning = None
         self._packed: Optional[torch.Tensor] = None
+        self._pack_path: Optional[str] = None
         self._packed_key = None
         self._packed_event = None
         self._packed_stream = None
@@ -176,7 +184,7 @@ class TokenPacker(nn.Module):
         self._bwd_sat_warned, self._bwd_sat_pending = False, None      # the backward workspace's status word (fp16 gradient chain)
 
     # ------------------------------------------------------------------------------------------
-    _CACHE_DEFAULTS = {"tuning": None, "_packed": None, "_packed_key": None, "_packed_event": None, "_packed_stream": None,
+    _CACHE_DEFAULTS = {"tuning": None, "_packed": None, "_pack_path": None, "_packed_key": None, "_packed_event": None, "_packed_stream": None,
                        "_overflow_checked": False, "_last_launch": None, "_sat_warned": False, "_sat_pending": None,
                        "_sat_count": 0, "_bwd_sat_warned": False, "_bwd_sat_pending": None}
 
@@ -195,6 +203,7 @@ class TokenPacker(nn.Module):
         self.__dict__.setdefault("_workspaces", {})
         self.__dict__.setdefault("input_gradients", False)        # (modules pickled before the switch existed)
         self.__dict__.setdefault("use_main_grad", False)
+        self.__dict__.setdefault("host_cast_weights", False)
 
     def _reset_parameters(self) -> None:
         """Same initial distribution as the reference (builder.py:87-94): truncated normal
@@ -268,6 +277,20 @@ class TokenPacker(nn.Module):
             out.append((name, p, checked_main_grad(name, p)))
         return out
 
+    @property
+    def last_pack_path(self) -> Optional[str]:
+        """Where the last weight pack read the parameters from: ``"raw_f32"`` — the fp32 parameters themselves, rounded on the
+        device (``TP_DESC_RAW_F32``) —, ``"host_cast"`` — compute-dtype tensors made by ``.to(dtype)`` (the parameters themselves
+        when they already are in that dtype) —, or ``None`` before the first pack.  Read-only."""
+        return self._pack_path
+
+    def _reads_raw_f32(self, weights, dtype: torch.dtype, device: torch.device) -> bool:
+        """Whether the library can read ``weights`` in place as fp32 master weights (see ``host_cast_weights``)."""
+        return (not self.host_cast_weights and dtype in _DTYPES
+                and all(w.dtype == torch.float32 and w.device == device and w.is_contiguous() and w.data_ptr() % 16 == 0
+                        for w in weights)
+                and _capi.raw_f32_supported())
+
     def _ln_eps(self) -> float:
         return float(self.ln_q_1.eps)
 
@@ -313,8 +336,10 @@ class TokenPacker(nn.Module):
                 raise TypeError(f"parameter {name} is {w.dtype}, inputs are {dtype}: cast the module with .to({dtype}) like "
                                 f"the reference does, or run under torch.autocast")
         lib = _capi.load_library()
-        desc = _capi.make_desc(1, self.raw_grid, self.scale_factor, self.hidden_size, _DTYPES[dtype],
-                               ln_eps=self._ln_eps(), flags=_capi.TP_DESC_TRAIN_PACK if force else 0, tuning=self.tuning)
+        raw_f32 = self._reads_raw_f32(weights, dtype, device)
+        desc = _capi.make_desc(1, self.raw_grid, self.scale_factor, self.hidden_size, _DTYPES[dtype], ln_eps=self._ln_eps(),
+                               flags=(_capi.TP_DESC_TRAIN_PACK if force else 0) | (_capi.TP_DESC_RAW_F32 if raw_f32 else 0),
+                               tuning=self.tuning)
         nbytes = lib.tp_packed_weight_bytes(ctypes.byref(desc))
         if nbytes == 0:
             raise RuntimeError(f"tp_packed_weight_bytes: {_capi.last_error()}")
@@ -322,9 +347,11 @@ class TokenPacker(nn.Module):
         # the library keeps a host-side note per image ADDRESS; when this tensor dies its address goes back to the caching
         # allocator, so the note goes too (tp_pack_forget) — a later tensor at the same address is not judged by it
         weakref.finalize(packed, _forget_packed, packed.data_ptr()).atexit = False    # (never during interpreter teardown)
-        # fp32 master weights (autocast / fp32_compute_dtype) are rounded to the compute dtype here, like autocast does
-        contiguous = [w.detach().to(dtype).contiguous() for w in weights]      # keeps temporaries alive until enqueued
+        # fp32 master weights (autocast / fp32_compute_dtype) are rounded to the compute dtype like autocast does: by the pack's
+        # own kernels as they load them (raw_f32: no cast, no copy), or here
+        contiguous = weights if raw_f32 else [w.detach().to(dtype).contiguous() for w in weights]   # (temporaries live until enqueued)
         raw = _capi.tp_weights(*[t.data_ptr() for t in contiguous])
+        self.__dict__["_pack_path"] = "raw_f32" if raw_f32 else "host_cast"
         _capi.check(lib.tp_pack_weights(ctypes.byref(desc), ctypes.byref(raw), packed.data_ptr(), nbytes,
                                         stream_ptr), "tp_pack_weights")
         if not force or not self._overflow_checked:
@@ -645,9 +672,13 @@ class TokenPacker(nn.Module):
             stream_ptr = torch.cuda.current_stream(device).cuda_stream
             lib = _capi.load_library()
             # `packed` is the image the forward of THIS step ran on; fp32 master weights (autocast) are rounded to the
-            # compute dtype for the dgrad operands exactly as they were for the forward
-            contiguous = [p.detach().to(x_multi.dtype).contiguous() for p in params]
+            # compute dtype for the dgrad operands exactly as they were for the forward — on load (raw_f32), or here
+            raw_f32 = self._reads_raw_f32(params, x_multi.dtype, device)
+            contiguous = params if raw_f32 else [p.detach().to(x_multi.dtype).contiguous() for p in params]
             raw = _capi.tp_weights(*[t.data_ptr() for t in contiguous])
+            if raw_f32:                          # (a copy: the descriptor of the forward stays as it was)
+                desc = _capi.tp_desc.from_buffer_copy(desc)
+                desc.flags |= _capi.TP_DESC_RAW_F32
             grads = sink = None
             if main is not None:                 # (the parameters as they are NOW: the ones whose main_grad the caller reads)
                 targets = [mg if w else None for w, (_, _, mg) in zip(wanted, main)]
@@ -656,7 +687,7 @@ class TokenPacker(nn.Module):
                 sink = _capi.tp_grad_sink(_capi.tp_grads(*[t.data_ptr() if t is not None else None for t in targets]),
                                           _capi.TP_F32, 1)
             elif any(wanted):
-                grads = [torch.empty_like(t) if w else None for t, w in zip(contiguous, wanted)]
+                grads = [torch.empty(t.shape, dtype=x_multi.dtype, device=device) if w else None for t, w in zip(contiguous, wanted)]
                 sink = _capi.tp_grad_sink(_capi.tp_grads(*[t.data_ptr() if t is not None else None for t in grads]),
                                           _DTYPES[x_multi.dtype], 0)
             g_arg = ctypes.byref(sink) if sink is not None else None

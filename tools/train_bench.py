@@ -16,6 +16,10 @@ inputs requiring grad) and prices the two extra dgrads: dx_multi = dZ1 · [Wk0; 
 --mask also times the step with an attn_mask that is a learnable region bias (a float mask requiring grad: the masked attention
 backward and dL/dmask): the 2-D [1, s*s] form (dmask summed over every image, query and head) and the 3-D [(M*B)*8, 1, s*s]
 form (every entry written once).
+--amp times the step of an fp32 module under torch.autocast(bf16) — fp32 master weights, what the reference's train.py runs outside
+DeepSpeed's bf16 engine: the library reads the fp32 parameters in place (module.last_pack_path == "raw_f32"); --host-cast forces the
+host-side casts instead (the A/B).  With --optimizer main_grad_adamw the fp32 parameters are their own masters.  HIP only.
+--reps R repeats the timing of the step R times in one process and reports every repetition and their median.
 --trainable not_kv / mlp times the step of a partially frozen projector (the K/V branches frozen; only mlp.* trainable): the backward
 computes the gradients of the parameters that require one and nothing else (tp_backward_sink).  HIP only: no eager baseline.
 """
@@ -74,6 +78,9 @@ def main():
     ap.add_argument("--mask", action="store_true", help="also time the step with a learnable attn_mask (2-D and 3-D float)")
     ap.add_argument("--trainable", default="all", choices=["all", "not_kv", "mlp"],
                     help="freeze the K/V branches (k_proj_1, v_proj_1, ln_k_1, ln_v_1), or everything but mlp.* (implies --hip-only)")
+    ap.add_argument("--amp", action="store_true", help="fp32 parameters under torch.autocast(bf16) (implies --hip-only)")
+    ap.add_argument("--host-cast", action="store_true", help="with --amp: force the host-side casts (module.host_cast_weights)")
+    ap.add_argument("--reps", type=int, default=1, help="repetitions of the step's timing; the median is reported")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE", help="library tuning knob, e.g. BWD_CHAIN=1")
     args = ap.parse_args()
     from tokenpacker_amd import _capi
@@ -81,12 +88,15 @@ def main():
         key, val = kv.split("=")
         _capi.set_tuning(getattr(_capi, "TP_TUNE_" + key.upper()), int(val))
     s, D, dtype = args.scale_factor, args.hidden_size, torch.bfloat16
-    args.hip_only = args.hip_only or args.trainable != "all"
+    args.hip_only = args.hip_only or args.trainable != "all" or args.amp
+    import contextlib
+    autocast = (lambda: torch.autocast("cuda", dtype=dtype)) if args.amp else contextlib.nullcontext
     frozen = {"all": (), "not_kv": ("k_proj_1.", "v_proj_1.", "ln_k_1.", "ln_v_1."), "mlp": ("",)}[args.trainable]
     results = []
     for B in args.batches:
         torch.manual_seed(0)
-        m = TokenPacker(hidden_size=D, scale_factor=s).to(device="cuda", dtype=dtype)
+        m = TokenPacker(hidden_size=D, scale_factor=s).to(device="cuda", dtype=torch.float32 if args.amp else dtype)
+        m.host_cast_weights = args.host_cast
         for name, p in m.named_parameters():
             if name.startswith(frozen) and not (args.trainable == "mlp" and name.startswith("mlp.")):
                 p.requires_grad_(False)
@@ -97,8 +107,11 @@ def main():
 
         import copy
         m_eager = copy.deepcopy(m)                       # each pipeline trains its own copy of the weights
-        opt = torch.optim.SGD([p for p in m.parameters() if p.requires_grad], lr=1e-7) if args.optimizer == "sgd" else None
-        opt_e = torch.optim.SGD(m_eager.parameters(), lr=1e-7) if args.optimizer == "sgd" else None
+        # (the objective sum(y * w) is linear in y and has no minimum: bf16 parameters round a 1e-7 update away, fp32 parameters
+        # take it, and mlp.* then grows without bound — non-finite after a few hundred steps.  --amp steps 1000 x shorter: same work.)
+        lr_sgd = 1e-10 if args.amp else 1e-7
+        opt = torch.optim.SGD([p for p in m.parameters() if p.requires_grad], lr=lr_sgd) if args.optimizer == "sgd" else None
+        opt_e = torch.optim.SGD(m_eager.parameters(), lr=lr_sgd) if args.optimizer == "sgd" else None
         clip_e = None
         if args.optimizer == "main_grad_adamw":
             from tokenpacker_amd import MainGradAdamW
@@ -110,7 +123,9 @@ def main():
 
         def step_hip():
             m.zero_grad(set_to_none=True)
-            (m((x, xm)) * w).sum().backward()
+            with autocast():
+                y = m((x, xm))
+            (y * w).sum().backward()
             if opt is not None:
                 opt.step()
 
@@ -123,7 +138,7 @@ def main():
                 opt_e.step()
 
         def fwd_hip():
-            with torch.no_grad():
+            with torch.no_grad(), autocast():
                 m((x, xm))
 
         x_in, xm_in = x.clone().requires_grad_(True), xm.clone().requires_grad_(True)
@@ -151,8 +166,13 @@ def main():
                 opt.step()
 
         iters = 20 if B <= 64 else 8
-        ms_hip = timed(step_hip, iters)
+        reps = sorted(timed(step_hip, iters) for _ in range(max(args.reps, 1)))
+        ms_hip = reps[len(reps) // 2] if len(reps) % 2 else 0.5 * (reps[len(reps) // 2 - 1] + reps[len(reps) // 2])
         ig = {}
+        if args.reps > 1:
+            ig["hip_fwd_bwd_ms_reps"] = [round(r, 3) for r in reps]
+        if args.amp:
+            ig.update({"amp": True, "optimizer_in_step": args.optimizer, "pack_path": getattr(m, "last_pack_path", None)})
         if args.mask:
             for kind, mask in masks.items():
                 ms_mask = timed(lambda: step_hip_mask(mask), iters)
@@ -170,7 +190,9 @@ def main():
         # (ln_k_1.bias and the k third of in_proj_bias have a mathematically zero gradient: round-off in both)
         E = 1024
         if args.hip_only:
-            rec = {"B": B, "trainable": args.trainable, "hip_fwd_bwd_ms": round(ms_hip, 3), "hip_fwd_only_ms": round(ms_fwd, 3), **ig}
+            if args.amp:
+                ig["weights_finite_after_training"] = all(bool(torch.isfinite(p).all()) for p in m.parameters())
+            rec ={"B": B, "trainable": args.trainable, "hip_fwd_bwd_ms": round(ms_hip, 3), "hip_fwd_only_ms": round(ms_fwd, 3), **ig}
             print(json.dumps(rec), flush=True)
             results.append(rec)
             del m, x, xm, w, x_in, xm_in, masks
