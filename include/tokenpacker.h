@@ -44,6 +44,8 @@ extern "C" {
 /* ABI 6, extended a fourth time (by symbol, the version stays 6): tp_desc_known_flags, TP_DESC_RAW_F32 (the raw parameters handed to
  * tp_pack_weights / tp_backward* may be fp32 master weights, read in place) and tp_optim_hyper.dtype = TP_F32 (AdamW on fp32
  * parameters that are their own masters).  Without the flag / with a 16-bit optimizer dtype nothing changes, bits included. */
+/* ABI 6, extended a fifth time (by symbol, the version stays 6): tp_optim_sumsq and tp_optim_apply — tp_optim_step cut in two with
+ * room for a collective in between, for an optimizer whose state is sharded across ranks.  tp_optim_step is unchanged, bits included. */
 #define TP_ABI_VERSION 6
 
 typedef enum tp_status {
@@ -546,6 +548,35 @@ typedef struct tp_optim_state {
 size_t tp_optim_workspace_bytes(const tp_optim_tensor* t, int n);
 int tp_optim_step(const tp_optim_tensor* t, int n, const tp_optim_hyper* h, const float* inv_scale, void* state, void* workspace,
                   size_t workspace_bytes, void* stream);
+
+/* ---- sharded optimizer step: tp_optim_step in two calls (ABI 6 extension, detected by symbol) ------------------------------
+ * For an optimizer whose moments, masters and update are sharded across W ranks (ZeRO-1): every rank holds a table over ITS shard of
+ * the reduced gradients, and the global norm needs one collective between the two calls:
+ *     tp_optim_sumsq (this rank's sum of squares -> one device double)  ->  all-gather of the W doubles, in rank order
+ *     ->  tp_optim_apply (the W doubles -> the state block -> AdamW on this rank's table)
+ * Both multiply every gradient by s = (inv_scale ? inv_scale[0] : 1) * grad_scale, one fp32 product, before anything else;
+ * grad_scale is a HOST float, finite and > 0: the 1 / W of gradient averaging behind a summing reduce-scatter (1: the bits of
+ * inv_scale alone).  tp_optim_step is these two calls with grad_scale = 1 and nsums = 1, bit for bit.
+ *
+ *   tp_optim_sumsq   the fp32 sum of (grad * s)^2 per chunk into `workspace` (one float per chunk: tp_optim_workspace_bytes is
+ *                    enough, 16-byte aligned), exactly tp_optim_step's first launches; then ONE workgroup adds the chunks' sums in
+ *                    fp64 in tp_optim_step's fixed order (a contiguous run per lane, then the neighbour tree) into sumsq_out[0]
+ *                    (a device double, 8-byte aligned).  Only `grad` and `numel` of each entry are read.  n == 0 is legal — a rank
+ *                    whose shard is all padding still takes part — and writes 0.0; its workspace may be NULL.
+ *   tp_optim_apply   one workgroup adds sums[0 .. nsums) (device doubles, 8-byte aligned, nsums >= 1) in index order in fp64 and
+ *                    derives the whole state block from the total exactly as tp_optim_step does (norm, clip_coef, found_inf, the
+ *                    step / skipped counters, bc1, sqrt_bc2: same formulas, same fp32 roundings); the AdamW kernel then runs over
+ *                    the table.  n == 0 still runs the first kernel: the counters advance on every rank alike.  A non-finite
+ *                    total skips the update of EVERY shard, also on a rank whose own gradients are finite.
+ * Determinism: the results depend on the table and on nsums, never on the grid or the device's CU count; every rank that is given
+ * the same `sums` writes the same state block.  TP_ERR_INVALID_ARG before anything is enqueued, under tp_optim_step's rules (the
+ * named entry, alignment, the same address twice, dtype, param == NULL for TP_F32; tp_optim_sumsq holds only `grad` to them), and
+ * for grad_scale <= 0 / NaN / inf, nsums < 1, a NULL or misaligned sums / sumsq_out.  A table longer than 32 entries is served by
+ * consecutive launches.  Enqueue-only, reentrant, no atomics, allocates nothing. */
+int tp_optim_sumsq(const tp_optim_tensor* t, int n, const float* inv_scale, float grad_scale, double* sumsq_out, void* workspace,
+                   size_t workspace_bytes, void* stream);
+int tp_optim_apply(const tp_optim_tensor* t, int n, const tp_optim_hyper* h, const float* inv_scale, float grad_scale,
+                   const double* sums, int nsums, void* state, void* stream);
 
 /* The backward's weight-gradient contraction on its own (what autograd computes for every nn.Linear of
  * builder.py:59-83):  dw[n_out, k_in] = sum over the `rows` token rows of dy[r, n] * x[r, k], read from the ROW-MAJOR

@@ -61,7 +61,7 @@ EXPORTED_SYMBOLS = (
     "tp_backward_inputs_workspace_bytes", "tp_backward_inputs", "tp_backward_inputs_parts",
     "tp_forward_train_masked", "tp_forward_parts_masked", "tp_backward_masked",
     "tp_backward_sink", "tp_backward_plan",
-    "tp_optim_workspace_bytes", "tp_optim_step",
+    "tp_optim_workspace_bytes", "tp_optim_step", "tp_optim_sumsq", "tp_optim_apply",
     "tp_hd_assemble_backward_workspace_bytes", "tp_hd_assemble_backward",
     "tp_splice", "tp_splice_backward_workspace_bytes", "tp_splice_backward",
     "tp_desc_known_flags",
@@ -344,6 +344,13 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.tp_splice_backward.restype = c_int
     lib.tp_splice_backward.argtypes = [POINTER(tp_splice_args), c_void_p]
 
+    if hasattr(lib, "tp_optim_sumsq") and hasattr(lib, "tp_optim_apply"):     # (an ABI 6 extension — sharded_optim_supported())
+        lib.tp_optim_sumsq.restype = c_int
+        lib.tp_optim_sumsq.argtypes = [POINTER(tp_optim_tensor), c_int, c_void_p, c_float, c_void_p, c_void_p, c_size_t, c_void_p]
+        lib.tp_optim_apply.restype = c_int
+        lib.tp_optim_apply.argtypes = [POINTER(tp_optim_tensor), c_int, POINTER(tp_optim_hyper), c_void_p, c_float, c_void_p, c_int,
+                                       c_void_p, c_void_p]
+
     if hasattr(lib, "tp_desc_known_flags"):              # (an ABI 6 extension: an older build lacks it — raw_f32_supported())
         lib.tp_desc_known_flags.restype = c_int
         lib.tp_desc_known_flags.argtypes = []
@@ -444,6 +451,13 @@ def raw_f32_supported() -> bool:
     return _raw_f32
 
 
+def sharded_optim_supported() -> bool:
+    """Whether the loaded library has the sharded optimizer step (``tp_optim_sumsq`` / ``tp_optim_apply``): detected by symbol, an
+    older ABI 6 build lacks them."""
+    lib = load_library()
+    return hasattr(lib, "tp_optim_sumsq") and hasattr(lib, "tp_optim_apply")
+
+
 def make_desc(batch: int, raw_grid: int, scale_factor: int, hidden_size: int, dtype: int,
               out_dtype: int | None = None, ln_eps: float = 1e-6, flags: int = 0, tuning=None) -> tp_desc:
     """`tuning`: a TuningContext (or its raw handle) the call reads its knobs from; None = the process-wide table."""
@@ -529,5 +543,5 @@ def get_tuning(key: int) -> int:
 
 
 __all__ = [n for n in dir() if n.startswith(("TP_", "tp_"))] + [
-    "load_library", "load_test_library", "last_error", "check", "make_desc", "strides3", "backward_plan", "raw_f32_supported", "BWD_STAGE_NAMES", "set_tuning", "get_tuning", "TuningContext",
+    "load_library", "load_test_library", "last_error", "check", "make_desc", "strides3", "backward_plan", "raw_f32_supported", "sharded_optim_supported", "BWD_STAGE_NAMES", "set_tuning", "get_tuning", "TuningContext",
     "TokenPackerLibraryError", "WEIGHT_FIELDS", "EXPORTED_SYMBOLS", "TEST_SYMBOLS", "LIB_PATH", "EXP_LIB_PATH", "byref"]

@@ -152,7 +152,7 @@ class TokenPacker(nn.Module):
         #: (``init_main_grads()`` makes them, ``zero_main_grads()`` clears them at the start of a step) — and every backward ADDS its
         #: gradient to it, unrounded (micro-batch accumulation without the two roundings per micro-step of ``bf16 .grad += bf16 g``;
         #: two calls of the module in one step both accumulate).  ``p.grad`` stays ``None``: autograd is told nothing about these
-        #: gradients, so DDP / ZeRO gradient hooks do NOT fire in this mode — the caller reduces ``main_grad`` across ranks itself.
+        #: gradients, so DDP / ZeRO gradient hooks do NOT fire in this mode — ``optim.ShardedMainGradAdamW`` reduces ``main_grad`` across ranks.
         #: Input and mask gradients are not affected.
         self.use_main_grad = False
         #: fp32 callers.  The reference module runs in any dtype; the HIP kernels compute in bf16 / fp16 MFMA.  Under
