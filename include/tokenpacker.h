@@ -703,6 +703,40 @@ int tp_splice_backward(const tp_splice_args* args, void* stream);
 int tp_hd_slice(const float* image, int H, int W, int h_block, int w_block, int h_res, int w_res, int hg, int wg,
                 float* crops, int block, void* stream);
 
+/* ---- HD slicing from uint8 images: a batch per launch, normalised on the device ------------------------------------
+ * (An ABI 6 extension, detected by symbol: an older ABI 6 build lacks tp_hd_slice_u8.)
+ * Everything the reference's loader does between the decoded picture and the tower (train.py:696-731 and the driver's
+ * `.to(dtype)`), for a whole batch of raw RGB uint8 images of different sizes, as ONE launch: ToTensor + Normalize,
+ * resize, zero-pad, tile and global view, stored in `out_dtype` (TP_F32, TP_BF16 or TP_F16) with one rounding
+ * (round to nearest even, Tensor.to).
+ *   pixels [pixel_bytes]  device bytes; image i is HWC uint8, pixel (y, x) at src_offset + y * row_stride + 3 * x.
+ *                         pixel_bytes >= 8: a tap is fetched by one 8-byte load, moved down where it would end past the
+ *                         buffer — no address outside pixels[0, pixel_bytes) is ever formed.
+ *   lut [3][256] fp32     device table: lut[c][u] = fl(fl(fl(u / 255) - mean_c) / std_c), built on the host (true
+ *                         divisions, tokenpacker_amd.hd.normalisation_table); the kernel keeps it in LDS and does no
+ *                         division of its own — the normalisation is bit-exact by construction.
+ *   crops [n_crops, 3, block, block]   16-byte aligned; block % 8 == 0 (a lane stores 8 consecutive pixels, 16 bytes per
+ *                         channel plane).  Image i owns crops [first_crop, first_crop + h_block * w_block (+ 1)), row-major,
+ *                         the global view last; the ranges are in image order, disjoint, and cover [0, n_crops).
+ * Resize arithmetic: tp_hd_slice's taps and blend on table values, zero outside (h_res, w_res); the global view is the
+ * canvas (padding included) resized to (hg, wg), computed from the canvas's fp32 values, not from rounded crops.
+ * The plan — the same words on the host (read by the validation) and on the device (read by the kernel) — is
+ * tp_hd_slice_image [n_images] followed by int32 [n_crops], the image index of every crop (a workgroup finds its image in
+ * O(1)).  plan_dev is 8-byte aligned.  The call validates on the host first (TP_ERR_INVALID_ARG: NULL or misaligned
+ * pointers, non-positive sizes, an image outside `pixels`, sizes that do not fit the grid, (hg, wg) != (0, 0) with one crop
+ * or 0 with several, crop ranges out of order / overlapping / not summing to n_crops, a crop mapped to another image,
+ * block, out_dtype), then only enqueues: no allocation, no atomics, no synchronisation.  The kernel checks the device copy
+ * of an entry again and writes zeros for one that fails. */
+typedef struct tp_hd_slice_image {
+    int64_t src_offset;            /* byte offset of pixel (0,0) in `pixels` */
+    int32_t H, W, row_stride;      /* row_stride in bytes, >= 3*W */
+    int32_t h_block, w_block, h_res, w_res, hg, wg;   /* hd.slice_plan's sizes; hg = wg = 0 iff one crop */
+    int32_t first_crop;
+} tp_hd_slice_image;
+int tp_hd_slice_u8(const tp_hd_slice_image* plan_host, const void* plan_dev, int n_images,
+                   const uint8_t* pixels, int64_t pixel_bytes, const float* lut /* device [3][256] */,
+                   void* crops, int64_t n_crops, int block, int out_dtype /* TP_F32 | TP_BF16 | TP_F16 */, void* stream);
+
 /* ---- debug: fp16 saturation scan ---------------------------------------------------------------------------------
  * Every activation between the kernels of tp_forward is fp16 and every epilogue CLAMPS to +-65504 instead of producing
  * inf.  After a tp_forward on `stream` with the same desc / workspace, this scans the nine intermediate

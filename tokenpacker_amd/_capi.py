@@ -64,7 +64,7 @@ EXPORTED_SYMBOLS = (
     "tp_optim_workspace_bytes", "tp_optim_step", "tp_optim_sumsq", "tp_optim_apply",
     "tp_hd_assemble_backward_workspace_bytes", "tp_hd_assemble_backward",
     "tp_splice", "tp_splice_backward_workspace_bytes", "tp_splice_backward",
-    "tp_desc_known_flags",
+    "tp_desc_known_flags", "tp_hd_slice_u8",
     "tp_tuning_create", "tp_tuning_destroy", "tp_tuning_set", "tp_tuning_get", "tp_gather_alloc_flags", "tp_gather_free_flags", "tp_gather_export", "tp_gather_open", "tp_gather_close", "tp_gather_push", "tp_gather_sync",
 )
 # include/tokenpacker_test.h: the stateless test hooks — libtokenpacker_exp.so only (load_test_library()), never the product library
@@ -167,6 +167,13 @@ class tp_linear_args(Structure):
 class tp_hd_image(Structure):
     _fields_ = [("first_crop", c_int32), ("h_block", c_int32), ("w_block", c_int32), ("reserved", c_int32),
                 ("out_row", c_int64)]
+
+
+class tp_hd_slice_image(Structure):
+    """One image of tp_hd_slice_u8's plan: where its HWC uint8 bytes lie, hd.slice_plan's sizes and its first crop."""
+    _fields_ = [("src_offset", c_int64), ("H", c_int32), ("W", c_int32), ("row_stride", c_int32),
+                ("h_block", c_int32), ("w_block", c_int32), ("h_res", c_int32), ("w_res", c_int32), ("hg", c_int32), ("wg", c_int32),
+                ("first_crop", c_int32)]
 
 
 TP_SPLICE_TEXT, TP_SPLICE_LITERAL, TP_SPLICE_FEATURE, TP_SPLICE_PAD = 0, 1, 2, 3
@@ -355,6 +362,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.tp_desc_known_flags.restype = c_int
         lib.tp_desc_known_flags.argtypes = []
 
+    if hasattr(lib, "tp_hd_slice_u8"):                   # (an ABI 6 extension — hd_slice_u8_supported())
+        lib.tp_hd_slice_u8.restype = c_int
+        lib.tp_hd_slice_u8.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                       c_void_p]
+
     if lib.tp_version() != TP_ABI_VERSION:
         raise TokenPackerLibraryError(
             f"{path}: ABI version {lib.tp_version()} != expected {TP_ABI_VERSION}; rebuild the library")
@@ -458,6 +470,12 @@ def sharded_optim_supported() -> bool:
     return hasattr(lib, "tp_optim_sumsq") and hasattr(lib, "tp_optim_apply")
 
 
+def hd_slice_u8_supported() -> bool:
+    """Whether the loaded library slices batches of uint8 images (``tp_hd_slice_u8``): detected by symbol, an older ABI 6 build
+    lacks it."""
+    return hasattr(load_library(), "tp_hd_slice_u8")
+
+
 def make_desc(batch: int, raw_grid: int, scale_factor: int, hidden_size: int, dtype: int,
               out_dtype: int | None = None, ln_eps: float = 1e-6, flags: int = 0, tuning=None) -> tp_desc:
     """`tuning`: a TuningContext (or its raw handle) the call reads its knobs from; None = the process-wide table."""
@@ -543,5 +561,5 @@ def get_tuning(key: int) -> int:
 
 
 __all__ = [n for n in dir() if n.startswith(("TP_", "tp_"))] + [
-    "load_library", "load_test_library", "last_error", "check", "make_desc", "strides3", "backward_plan", "raw_f32_supported", "sharded_optim_supported", "BWD_STAGE_NAMES", "set_tuning", "get_tuning", "TuningContext",
+    "load_library", "load_test_library", "last_error", "check", "make_desc", "strides3", "backward_plan", "raw_f32_supported", "sharded_optim_supported", "hd_slice_u8_supported", "BWD_STAGE_NAMES", "set_tuning", "get_tuning", "TuningContext",
     "TokenPackerLibraryError", "WEIGHT_FIELDS", "EXPORTED_SYMBOLS", "TEST_SYMBOLS", "LIB_PATH", "EXP_LIB_PATH", "byref"]

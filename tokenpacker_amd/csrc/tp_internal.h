@@ -52,6 +52,19 @@ template <typename T, typename S> __device__ __forceinline__ typename Vec<T>::x8
         return *(const typename Vec<T>::x8*)p;
     }
 }
+// The two taps and weights of output index `dst` of a bilinear resize (F.interpolate, align_corners = False, no antialias):
+// src = scale (dst + 0.5) - 0.5 clamped at 0, scale = in / out in fp32.  Shared by tp_hd_slice (tp_kernels.hip) and
+// tp_hd_slice_u8 (tp_hd_slice.hip): one arithmetic for both.
+__host__ __device__ __forceinline__ void bilinear_taps(float scale, int dst, int in_size, int& i0, int& i1, float& l0, float& l1) {
+    float src = scale * ((float)dst + 0.5f) - 0.5f;
+    src = src < 0.f ? 0.f : src;
+    i0 = (int)src;
+    i0 = i0 < in_size - 1 ? i0 : in_size - 1;
+    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
+    l1 = src - (float)i0;
+    l1 = fminf(fmaxf(l1, 0.f), 1.f);
+    l0 = 1.f - l1;
+}
 #endif
 
 // ---- error plumbing ---------------------------------------------------------------------------

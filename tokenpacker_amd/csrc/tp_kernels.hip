@@ -692,18 +692,7 @@ int hd_assemble_bwd_launch(const tp_hd_image* plan, int n_images, const void* do
 // in the top-left corner of a zero canvas of h_block x w_block blocks of `block` pixels, and the canvas is cut
 // into crops (row-major).  With more than one crop a global view follows: the CANVAS (padding included — the
 // reference re-uses the variable, train.py:710,728) resized to (hg, wg) and zero-padded to block x block.
-// One thread per output pixel; crops [n, 3, block, block] fp32.
-__device__ __forceinline__ void bilinear_taps(float scale, int dst, int in_size, int& i0, int& i1, float& l0, float& l1) {
-    float src = scale * ((float)dst + 0.5f) - 0.5f;
-    src = src < 0.f ? 0.f : src;
-    i0 = (int)src;
-    i0 = i0 < in_size - 1 ? i0 : in_size - 1;
-    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-    l1 = src - (float)i0;
-    l1 = fminf(fmaxf(l1, 0.f), 1.f);
-    l0 = 1.f - l1;
-}
-
+// One thread per output pixel; crops [n, 3, block, block] fp32.  (bilinear_taps: tp_internal.h, shared with tp_hd_slice.hip.)
 __global__ void __launch_bounds__(256)
 hd_slice_crops_kernel(const float* __restrict__ img, int H, int W, int h_block, int w_block, int h_res, int w_res,
                       float* __restrict__ crops, int block) {

@@ -2,6 +2,9 @@
 
 * :func:`select_grid` — the crop-grid choice for one image (host-side scalar math; reference
   ``llava/patch_divide.py:71-104`` ``Image_Patch.calculate``).  Pure CPU, like the reference.
+* :func:`slice_image` — resize / zero-pad / tile / global view of ONE normalised fp32 image on the device (``tp_hd_slice``);
+  :func:`slice_images` — the same for a BATCH of raw RGB uint8 images, ``ToTensor`` + ``Normalize`` and the cast to the tower's
+  dtype included, from one launch (``tp_hd_slice_u8``; reference ``llava/train/train.py:696-731``).
 * :func:`hd_token_rows`, :func:`assemble_hd_tokens` — what ``prepare_inputs_labels_for_multimodal`` does
   with the projected crops in ``mode == 'slice'`` (reference ``llava/model/llava_arch.py:140-154``): the crops
   of one image row are joined with the ``','`` token embedding, every row and the trailing global view end
@@ -15,8 +18,9 @@
 from __future__ import annotations
 
 import ctypes
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _capi
@@ -89,6 +93,184 @@ def slice_image(image: torch.Tensor, patch_num: int = 9, block: int = 336):
         _capi.check(lib.tp_hd_slice(image.data_ptr(), H, W, hb, wb, h_res, w_res, hg, wg, crops.data_ptr(), block,
                                     torch.cuda.current_stream(image.device).cuda_stream), "tp_hd_slice")
     return crops, hb, wb
+
+
+CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)        # the reference's Normalize (train.py:645, every eval driver)
+CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+
+
+def normalisation_table(mean: Sequence[float] = CLIP_MEAN, std: Sequence[float] = CLIP_STD) -> torch.Tensor:
+    """``[3, 256]`` fp32 on the CPU: entry ``[c, u]`` is what ``Compose([ToTensor(), Normalize(mean, std)])`` makes of byte
+    ``u`` in channel ``c`` — ``fl(fl(fl(u / 255) - mean_c) / std_c)``, computed with the CPU ops torchvision itself runs, in its
+    order (true divisions, not multiplications by a reciprocal).  The value depends on ``(c, u)`` only, so a lookup in this
+    table IS the reference's normalisation, bit for bit."""
+    mean, std = _table_key(mean, std)
+    m, s = torch.tensor(mean, dtype=torch.float32), torch.tensor(std, dtype=torch.float32)
+    return torch.arange(256).to(torch.float32).div(255).sub(m[:, None]).div(s[:, None])
+
+
+def _table_key(mean, std):
+    mean, std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("mean and std must have three entries (RGB)")
+    if 0.0 in std:
+        raise ValueError("std must be non-zero")
+    return mean, std
+
+
+_table_cache = {}
+
+
+def _device_table(key, device: torch.device) -> torch.Tensor:
+    """The table on ``device``: uploaded once per (mean, std, device)."""
+    t = _table_cache.get((key, device))
+    if t is None:
+        t = _table_cache[(key, device)] = normalisation_table(*key).to(device)
+    return t
+
+
+_PLAN_IMAGE = np.dtype([("src_offset", "<i8"), ("H", "<i4"), ("W", "<i4"), ("row_stride", "<i4"), ("h_block", "<i4"),
+                        ("w_block", "<i4"), ("h_res", "<i4"), ("w_res", "<i4"), ("hg", "<i4"), ("wg", "<i4"), ("first_crop", "<i4")])
+_PIXEL_ALIGN = 16
+
+
+class SliceBatchPlan(NamedTuple):
+    """Host plan of one :func:`slice_images` call.  ``images``: one ``tp_hd_slice_image`` record per image (a numpy structured
+    array with the C struct's layout); ``crop_image`` (int32 ``[n_crops]``): the image of every crop; ``pixel_bytes``: the size
+    of the pixel buffer the offsets address."""
+    images: np.ndarray
+    crop_image: np.ndarray
+    h_block: List[int]
+    w_block: List[int]
+    n_crops: int
+    pixel_bytes: int
+
+    def words(self) -> np.ndarray:
+        """The plan as the bytes ``tp_hd_slice_u8`` reads: the image records, then the crop-to-image index."""
+        return np.concatenate([self.images.view(np.uint8), self.crop_image.view(np.uint8)])
+
+
+def slice_batch_plan(sizes: Sequence[Tuple[int, int]], patch_num: int = 9, block: int = 336,
+                     row_strides: Optional[Sequence[int]] = None, offsets: Optional[Sequence[int]] = None) -> SliceBatchPlan:
+    """The plan for images of ``sizes [(H, W), ...]``: grids and sizes from :func:`slice_plan`, consecutive crop ranges, and
+    where each image's bytes lie.  ``row_strides`` (bytes, default ``3 W``: dense rows); ``offsets`` (byte offset of every
+    image's first pixel; default: the images packed one behind the other, each on a 16-byte boundary, which is how
+    :func:`slice_images` stages CPU images).  Pure host logic."""
+    n = len(sizes)
+    if n == 0:
+        raise ValueError("slice_batch_plan: no images")
+    images = np.zeros(n, dtype=_PLAN_IMAGE)
+    hbs, wbs, owner, first, at = [], [], [], 0, 0
+    for i, (H, W) in enumerate(sizes):
+        H, W = int(H), int(W)
+        if H < 1 or W < 1:
+            raise ValueError(f"image {i}: size {H} x {W}")
+        stride = 3 * W if row_strides is None else int(row_strides[i])
+        if stride < 3 * W or stride > 0x7FFFFFFF:
+            raise ValueError(f"image {i}: row stride {stride} (3 * W = {3 * W} .. 2^31 - 1)")
+        hb, wb, h_res, w_res, hg, wg = slice_plan(H, W, patch_num, block)
+        if min(h_res, w_res) < 1 or (hb * wb > 1 and min(hg, wg) < 1):
+            raise ValueError(f"image {i}: {H} x {W} is too elongated, a resized side rounds to 0 pixels (resize {h_res} x {w_res}, "
+                             f"global view {hg} x {wg}); the reference's F.interpolate refuses such an image too")
+        off = at if offsets is None else int(offsets[i])
+        images[i] = (off, H, W, stride, hb, wb, h_res, w_res, hg, wg, first)
+        count = hd_crop_count(hb, wb)
+        owner.append(np.full(count, i, dtype=np.int32))
+        hbs.append(hb)
+        wbs.append(wb)
+        first += count
+        end = off + (H - 1) * stride + 3 * W
+        at = max(at, -(-end // _PIXEL_ALIGN) * _PIXEL_ALIGN)
+    if first > 0x7FFFFFFF:
+        raise ValueError("the batch exceeds 2^31 crops")
+    return SliceBatchPlan(images, np.concatenate(owner), hbs, wbs, first, at)
+
+
+def _as_hwc_uint8(img, i: int):
+    """One entry of ``slice_images``' input, checked: a ``[H, W, 3]`` uint8 torch tensor or numpy array."""
+    if not isinstance(img, (torch.Tensor, np.ndarray)):
+        raise TypeError(f"images[{i}] must be a torch.Tensor or a numpy array, not {type(img).__name__}")
+    if img.dtype != (torch.uint8 if isinstance(img, torch.Tensor) else np.uint8):
+        raise TypeError(f"images[{i}] must be uint8 (raw RGB bytes), not {img.dtype}")
+    if img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError(f"images[{i}] must be [H, W, 3] (RGB, channels last), got {tuple(img.shape)}")
+    if img.shape[0] < 1 or img.shape[1] < 1:
+        raise ValueError(f"images[{i}] is empty: {tuple(img.shape)}")
+    return img
+
+
+def slice_images(images, patch_num: int = 9, block: int = 336, dtype: torch.dtype = torch.bfloat16,
+                 mean: Sequence[float] = CLIP_MEAN, std: Sequence[float] = CLIP_STD, device=None):
+    """A batch of raw RGB images -> ``(crops [n_total, 3, block, block] in dtype, h_block list, w_block list)``: the
+    ``images`` / ``h_block`` / ``w_block`` of a collated batch of the reference's loader in ``'slice'`` mode
+    (train.py:696-731, then the driver's ``.to(dtype)``) — ToTensor + Normalize, resize, zero-pad, tile and global view of
+    every image from ONE launch (``tp_hd_slice_u8``).
+
+    ``images``: a sequence of ``[H, W, 3]`` uint8 torch tensors or numpy arrays (``np.asarray(pil.convert("RGB"))``) of any
+    sizes; rows need not be contiguous.  CPU images and the plan are packed into one pinned staging buffer and travel in one
+    asynchronous copy — 3 bytes per pixel; device images (all on one device) are packed with one ``torch.cat`` of their bytes.
+    ``dtype``: float32, bfloat16 or float16 — one rounding at the store.  ``block`` must be a multiple of 8."""
+    if isinstance(images, (torch.Tensor, np.ndarray)) or not isinstance(images, Sequence):
+        raise TypeError("images must be a sequence (list / tuple) of [H, W, 3] uint8 images")
+    if len(images) == 0:
+        raise ValueError("images is empty")
+    imgs = [_as_hwc_uint8(img, i) for i, img in enumerate(images)]
+    out_dt = {torch.float32: _capi.TP_F32, torch.bfloat16: _capi.TP_BF16, torch.float16: _capi.TP_F16}.get(dtype)
+    if out_dt is None:
+        raise TypeError("dtype must be float32, bfloat16 or float16")
+    if block < 8 or block % 8 != 0:
+        raise ValueError(f"block = {block} must be a positive multiple of 8 (a lane stores 8 consecutive pixels)")
+    on_dev = [isinstance(img, torch.Tensor) and img.is_cuda for img in imgs]
+    if any(on_dev) and not all(on_dev):
+        raise ValueError("images must all be on the CPU or all on one device")
+    sizes = [(int(img.shape[0]), int(img.shape[1])) for img in imgs]
+    table_key = _table_key(mean, std)
+    if not torch.cuda.is_available():
+        raise RuntimeError("slice_images runs only on an AMD GPU (HIP kernel); there is no CPU fallback")
+    if not _capi.hd_slice_u8_supported():
+        raise RuntimeError("the loaded libtokenpacker_hip.so lacks tp_hd_slice_u8; rebuild it")
+    if on_dev[0]:
+        devices = {img.device for img in imgs}
+        if len(devices) != 1 or (device is not None and torch.device(device) != next(iter(devices))):
+            raise ValueError("device images must all live on one device (and `device`, when given, must be that one)")
+        dev = next(iter(devices))
+        pieces, strides, offsets, at = [], [], [], 0
+        for img, (H, W) in zip(imgs, sizes):
+            # rows of adjacent RGB bytes are read in place through their stride; anything else is made dense first
+            if img.stride(2) == 1 and img.stride(1) == 3 and (H == 1 or 3 * W <= img.stride(0) <= 0x7FFFFFFF):
+                stride = img.stride(0) if H > 1 else 3 * W
+            else:
+                img, stride = img.contiguous(), 3 * W
+            pieces.append(img.as_strided(((H - 1) * stride + 3 * W,), (1,)))
+            strides.append(stride)
+            offsets.append(at)
+            at += pieces[-1].numel()
+        if at < 8:
+            pieces.append(torch.zeros(8, dtype=torch.uint8, device=dev))
+            at += 8
+        plan = slice_batch_plan(sizes, patch_num, block, strides, offsets)._replace(pixel_bytes=at)
+    else:
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        plan = slice_batch_plan(sizes, patch_num, block)
+    words = plan.words()
+    pix_base = -(-words.size // _PIXEL_ALIGN) * _PIXEL_ALIGN
+    staging = torch.empty(pix_base + (0 if on_dev[0] else plan.pixel_bytes), dtype=torch.uint8, pin_memory=True)
+    stage_np = staging.numpy()
+    stage_np[:words.size] = words
+    if not on_dev[0]:
+        for img, rec, (H, W) in zip(imgs, plan.images, sizes):
+            at = pix_base + int(rec["src_offset"])
+            np.copyto(stage_np[at:at + H * W * 3].reshape(H, W, 3), img.numpy() if isinstance(img, torch.Tensor) else img)
+    crops = torch.empty(plan.n_crops, 3, block, block, dtype=dtype, device=dev)
+    lib = _capi.load_library()
+    with torch.cuda.device(dev):
+        lut = _device_table(table_key, dev)
+        staged_dev = staging.to(dev, non_blocking=True)                 # the one host -> device copy: plan (+ pixels)
+        pixels = torch.cat(pieces) if on_dev[0] else staged_dev[pix_base:]
+        _capi.check(lib.tp_hd_slice_u8(stage_np.ctypes.data, staged_dev.data_ptr(), len(imgs), pixels.data_ptr(), plan.pixel_bytes,
+                                       lut.data_ptr(), crops.data_ptr(), plan.n_crops, block, out_dt,
+                                       torch.cuda.current_stream(dev).cuda_stream), "tp_hd_slice_u8")
+    return crops, list(plan.h_block), list(plan.w_block)
 
 
 def hd_token_rows(h_block: int, w_block: int, num_queries: int) -> int:
