@@ -1102,6 +1102,7 @@ int forward_impl(const tp_desc* desc, const void* x, const int64_t x_strides[3],
         a.attn_logits = (float*)(ws + W.attn_aux);      // [8 heads][rows_kv] fp32
         a.attn_scale = 0.08838834764831845f;            // 1/sqrt(128): q scaling of F.multi_head_attention_forward
         a.attn_decoupled = decouple_k ? 1 : 0;
+        a.attn_centred = tri ? 1 : 0;                   // (mean = 0 in every row's statistics: the epilogues' short forms)
         if (decouple_k && kv == 0) return launch(TP_F16, TP_F16, a, st);     // (reads no statistics: stats_in is staged, never used)
         if (!merge_in_kernel(a, (const float*)(ws + W.stats_kv) + (size_t)kv * parts_kv * rows_kv * 2, 0)) TP_TRY(kv_finalize());
         else if (decouple_k) a.attn_kstats_parts = (const float*)(ws + W.stats_kv);      // (V launch: the K group's slabs as well)

@@ -149,7 +149,32 @@ gemm_kernel(const GemmArgs p, const int tiles_n, const int xcd_swizzle) {
 #pragma unroll
     for (int i = 0; i < FM; ++i) mean_rstd[i] = make_float2(0.f, 1.f);
     if (p.flags & TP_LINEAR_LN_FOLD) {
-        if (p.stats_parts) {                            // the producer's slabs, merged here (no ln_finalize launch):
+        if (p.stats_parts && p.ln_second_moment) {      // a triangular statistics GEMM's 16 second-moment partials [16][M], merged
+            float sm[FM][kSecondMomentParts];           // here in ln_finalize's order: every load of every row first, ONE wait
+#pragma unroll
+            for (int i = 0; i < FM; ++i) {
+                int m = m0 + wm * WM + i * 16 + (lane & 15);
+                m = m < p.M ? m : p.M - 1;
+#pragma unroll
+                for (int pp = 0; pp < kSecondMomentParts; ++pp)
+                    sm[i][pp] = p.stats_parts[g * p.stats_parts_gs + (long long)pp * p.M + m];
+            }
+#pragma unroll
+            for (int i = 0; i < FM; ++i) mean_rstd[i] = make_float2(0.f, ln_second_moment_rstd(sm[i], p.ln_inv_dim, p.ln_eps));
+            if constexpr (XMODE == 4) {
+                if (p.attn_kstats_parts) {              // decoupled attention: the K rows' rstd rides in the mean slot (GemmArgs::attn_decoupled)
+#pragma unroll
+                    for (int i = 0; i < FM; ++i) {
+                        int m = m0 + wm * WM + i * 16 + (lane & 15);
+                        m = m < p.M ? m : p.M - 1;
+#pragma unroll
+                        for (int pp = 0; pp < kSecondMomentParts; ++pp) sm[i][pp] = p.attn_kstats_parts[(long long)pp * p.M + m];
+                    }
+#pragma unroll
+                    for (int i = 0; i < FM; ++i) mean_rstd[i].x = ln_second_moment_rstd(sm[i], p.ln_inv_dim, p.ln_eps);
+                }
+            }
+        } else if (p.stats_parts) {                     // the producer's slabs, merged here (no ln_finalize launch):
             float2 st[FM][8];                           // every load of every row first, ONE wait, then the arithmetic
 #pragma unroll
             for (int i = 0; i < FM; ++i) {
@@ -160,20 +185,7 @@ gemm_kernel(const GemmArgs p, const int tiles_n, const int xcd_swizzle) {
                     st[i][pp] = *(const float2*)(p.stats_parts + g * p.stats_parts_gs + ((long long)pp * p.M + m) * 2);
             }
 #pragma unroll
-            for (int i = 0; i < FM; ++i) mean_rstd[i] = ln_merge_values<8>(st[i], p.ln_inv_dim, p.ln_eps, p.ln_second_moment != 0);
-            if constexpr (XMODE == 4) {
-                if (p.attn_kstats_parts) {              // decoupled attention: the K rows' rstd rides in the mean slot (GemmArgs::attn_decoupled)
-#pragma unroll
-                    for (int i = 0; i < FM; ++i) {
-                        int m = m0 + wm * WM + i * 16 + (lane & 15);
-                        m = m < p.M ? m : p.M - 1;
-#pragma unroll
-                        for (int pp = 0; pp < 8; ++pp) st[i][pp] = *(const float2*)(p.attn_kstats_parts + ((long long)pp * p.M + m) * 2);
-                    }
-#pragma unroll
-                    for (int i = 0; i < FM; ++i) mean_rstd[i].x = ln_merge_values<8>(st[i], p.ln_inv_dim, p.ln_eps, p.ln_second_moment != 0).y;
-                }
-            }
+            for (int i = 0; i < FM; ++i) mean_rstd[i] = ln_merge_values<8>(st[i], p.ln_inv_dim, p.ln_eps);
         } else {
 #pragma unroll
             for (int i = 0; i < FM; ++i) {

@@ -173,6 +173,53 @@ __device__ __forceinline__ void gemm_epilogue(f32x4 (&acc)[WM / 16][WN / 16], co
         }
     }
 
+    // Statistics-only tile of a TRIANGULAR statistics GEMM (GemmArgs::tri; tp_pack_qr.hip): the consumer wants the row's SECOND
+    // MOMENT  sum_n (acc_n + c~_n)^2  and nothing else (ln_merge_second_moment: (0, rstd)).  A sum of squares has no cancellation
+    // to guard against, so there is no pivot and no (mean, M2) pair: one packed FMA per two elements, the 4 lane groups of a row
+    // by xor 16 / xor 32, and lanes 0..15 of every wave write the wave's 64-column partial sums straight to global memory as
+    // stats_out[part = column / 64][row] (kSecondMomentParts = 16 fp32 per row and group — the bytes of the 8 float2 slabs).
+    // No LDS scratch and no barrier: the consumer adds the 16 partials in one fixed order, whatever kernel wrote them (a wave
+    // that owns 128 columns writes two partials), which is what keeps an image's bits independent of its batch.
+    // Every wave issues FM * VW store instructions per tile; rows past M get an offset past the end of the descriptor and are
+    // dropped by the hardware range check.
+    // Ping-pong kernel (tp_gemm8.hip): the epilogue's two workgroup barriers were executed by BOTH M-halves alike, so removing
+    // them leaves the halves' barrier counts equal; the one-barrier stagger of its hazard bookkeeping is made inside k_loop()
+    // (the late half's extra barrier at the start, the early half's at the re-join) and the next tile's DMA prologue is issued
+    // behind that re-join, before any epilogue — neither depends on a barrier in here.  The barrier that ends a tile's turn
+    // (parameters in LDS) is the caller's and stays.
+    if constexpr (STATS_ONLY) {
+        if (p.tri) {
+            const __amdgpu_buffer_rsrc_t rsrc_s = __builtin_amdgcn_make_buffer_rsrc(
+                (void*)(p.stats_out + g * p.stats_out_gs), 0, (int)(unsigned)((long long)kSecondMomentParts * p.M * 4), 0x00020000);
+            constexpr int VW2 = WN / 64, FNV2 = FN / VW2;
+#pragma unroll
+            for (int i = 0; i < FM; ++i) {
+                const int m = m0 + wm * WM + i * 16 + (lane & 15);
+#pragma unroll
+                for (int vs = 0; vs < VW2; ++vs) {
+                    f32x2_ev s = f32x2_ev{0.f, 0.f};
+#pragma unroll
+                    for (int jj = 0; jj < FNV2; ++jj) {
+                        const int j = vs * FNV2 + jj;
+                        f32x4 v = acc[i][j];
+                        if constexpr (LAZY_PAR) v += *(const f32x4*)(lds_par + (lc_lazy + j * 16) * 4);
+                        else v += bias_v[j];
+                        const f32x2_ev lo = f32x2_ev{v[0], v[1]}, hi = f32x2_ev{v[2], v[3]};
+                        s = __builtin_elementwise_fma(lo, lo, s);
+                        s = __builtin_elementwise_fma(hi, hi, s);
+                    }
+                    float t = s[0] + s[1];
+                    t += __shfl_xor(t, 16);
+                    t += __shfl_xor(t, 32);
+                    const int part = (n0 + wn * WN) / 64 + vs;
+                    const unsigned off = m < p.M ? (unsigned)(((long long)part * p.M + m) * 4) : 0xfffffff0u;
+                    if (lane < 16) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, t), rsrc_s, (int)off, 0, 0);
+                }
+            }
+            return;
+        }
+    }
+
     // Row statistics are accumulated per 64-column slice (VW slices per wave) and combined below in a fixed
     // tree, so a wave that owns 128 columns produces bit-identical results to two waves that own 64 each.
     // What travels is (mean, M2 = sum of squared deviations from that mean) of a group of values, merged pairwise by
@@ -380,6 +427,9 @@ __device__ __forceinline__ void gemm_epilogue(f32x4 (&acc)[WM / 16][WN / 16], co
 //   V launch  attn_sum_epilogue:    p = softmax over the quad's 4 logits (every lane computes the same p in the same order),
 //             w = p_row * V, summed over the quad with two DPP quad_perm adds; lane k of the quad stores fragment j = k:
 //             O[region][cols] fp16, 8 B per lane, FM stores per wave and tile instead of FM * FN / 2 of 16 B.
+//   On the centred chain (GemmArgs::attn_centred: every row mean is 0) both take short forms: the K launch's logit is
+//   rstd * (acc . q) — no bias, colsum or mean, the bias term being softmax-invariant — and the V launch multiplies once per
+//   element, (p * rstd) * acc, reduce-scatters the quad (12 DPP adds per fragment row) and adds the bias once.
 // The sums run in one fixed order whatever the tile shape (WN = 64 in every kernel), so the result does not depend on
 // the kernel a batch size selects.  `lds_q` (persistent kernel): the tile's queries [BM / 4][BN] fp16 staged in LDS;
 // `lds_par`: bias[BN] | colsum[BN] staged by the caller, and for the V launch the tile's logits [BN / 128][BM] at +LG_OFF.
@@ -395,16 +445,21 @@ __device__ __forceinline__ void attn_logits_epilogue(f32x4 (&acc)[WM / 16][WN / 
     static_assert(WN == 64 && BN % 128 == 0, "a head is two 64-column waves");
     const int cg = lane >> 4, r16 = lane & 15;
     const int col_base = n0 + wn * WN + cg * 4;
+    const bool raw = p.attn_decoupled || p.attn_centred;   // (wave-uniform) the raw accumulators: no bias, colsum or mean
     f32x4 bias_v[FN], csum_v[FN];
     if constexpr (LDS_PARAMS) {
         // (read from LDS at the point of use: 32 registers less across the epilogue of the persistent kernels)
     } else {
-        const float* __restrict__ bias = p.bias + g * p.bias_gs;
-        const float* __restrict__ colsum = p.colsum + g * p.colsum_gs;
 #pragma unroll
-        for (int j = 0; j < FN; ++j) {
-            bias_v[j] = *(const f32x4*)(bias + col_base + j * 16);
-            csum_v[j] = *(const f32x4*)(colsum + col_base + j * 16);
+        for (int j = 0; j < FN; ++j) bias_v[j] = csum_v[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (!raw) {
+            const float* __restrict__ bias = p.bias + g * p.bias_gs;
+            const float* __restrict__ colsum = p.colsum + g * p.colsum_gs;
+#pragma unroll
+            for (int j = 0; j < FN; ++j) {
+                bias_v[j] = *(const f32x4*)(bias + col_base + j * 16);
+                csum_v[j] = *(const f32x4*)(colsum + col_base + j * 16);
+            }
         }
     }
     // Q_LDS = false with staged parameters (tp_gemm_pair.hip): every query fragment of the wave's rows is fetched up front — one
@@ -422,43 +477,57 @@ __device__ __forceinline__ void attn_logits_epilogue(f32x4 (&acc)[WM / 16][WN / 
         }
     }
     float part[FM];
+    // Centred chain (GemmArgs::attn_centred: mu = 0) and decoupled — RAW: the dot product of the raw accumulators.  The bias term
+    // sum_c b_c q_c is the same for the 4 keys of a region, i.e. softmax-invariant, and is dropped; rstd scales the row's sum
+    // once (decoupled: in the V launch) — no bias, colsum or mean is read.  Register-carried parameters (the 128-tile kernel): two
+    // copies of the row loop under ONE wave-uniform branch — a branch per fragment inside the unrolled loops kept the per-row
+    // arrays in scratch there.  Staged parameters (the persistent kernels, no register to spare): one loop, the branch inside —
+    // there the second copy is what spilled.
+    auto rows = [&](auto MODE_) __attribute__((always_inline)) {
+        constexpr int MODE = decltype(MODE_)::value;       // 0 general | 1 raw | 2 decided per fragment (wave-uniform)
 #pragma unroll
-    for (int i = 0; i < FM; ++i) {
-        const int rr = wm * WM + i * 16 + r16;             // row inside the tile
-        float mu = mean_rstd[i].x, rstd = mean_rstd[i].y;
-        if constexpr (LDS_PARAMS) {                        // (read per fragment row: 14 registers less across the epilogue)
-            typedef float f32x2_t __attribute__((ext_vector_type(2)));
-            const f32x2_t mr = *(const f32x2_t*)(lds_par + 2 * BN * 4 + rr * 8);
-            mu = mr[0]; rstd = mr[1];
-        }
-        float d = 0.f;
-#pragma unroll
-        for (int j = 0; j < FN; ++j) {
-            f16x4 q;
-            if constexpr (Q_AHEAD) {
-                q = qv[i][j];
-            } else if constexpr (Q_LDS) {
-                q = *(const f16x4*)(lds_q + (rr >> 2) * (BN * 2) + (wn * WN + j * 16 + cg * 4) * 2);
-            } else {
-                int m = m0 + rr;
-                m = m < p.M ? m : p.M - 1;
-                q = *(const f16x4*)(p.attn_q + (long long)(m >> 2) * p.attn_ldq_bytes + (col_base + j * 16) * 2);
+        for (int i = 0; i < FM; ++i) {
+            const int rr = wm * WM + i * 16 + r16;         // row inside the tile
+            float mu = mean_rstd[i].x, rstd = mean_rstd[i].y;
+            if constexpr (LDS_PARAMS) {                    // (read per fragment row: 14 registers less across the epilogue)
+                typedef float f32x2_t __attribute__((ext_vector_type(2)));
+                const f32x2_t mr = *(const f32x2_t*)(lds_par + 2 * BN * 4 + rr * 8);
+                mu = mr[0]; rstd = mr[1];
             }
-            f32x4 bj, cj;
-            if constexpr (LDS_PARAMS) {
-                bj = *(const f32x4*)(lds_par + (wn * WN + cg * 4 + j * 16) * 4);
-                cj = *(const f32x4*)(lds_par + BN * 4 + (wn * WN + cg * 4 + j * 16) * 4);
-            } else { bj = bias_v[j]; cj = csum_v[j]; }
-            // (decoupled: the raw accumulators — rstd is applied by the V launch, the bias term is softmax-invariant)
-            const f32x4 v = p.attn_decoupled ? acc[i][j] : rstd * (acc[i][j] - mu * cj) + bj;
+            float d = 0.f;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) d = fmaf(v[r], (float)q[r], d);
+            for (int j = 0; j < FN; ++j) {
+                f16x4 q;
+                if constexpr (Q_AHEAD) {
+                    q = qv[i][j];
+                } else if constexpr (Q_LDS) {
+                    q = *(const f16x4*)(lds_q + (rr >> 2) * (BN * 2) + (wn * WN + j * 16 + cg * 4) * 2);
+                } else {
+                    int m = m0 + rr;
+                    m = m < p.M ? m : p.M - 1;
+                    q = *(const f16x4*)(p.attn_q + (long long)(m >> 2) * p.attn_ldq_bytes + (col_base + j * 16) * 2);
+                }
+                f32x4 v = acc[i][j];
+                if (MODE == 0 || (MODE == 2 && !raw)) {
+                    f32x4 bj, cj;
+                    if constexpr (LDS_PARAMS) {
+                        bj = *(const f32x4*)(lds_par + (wn * WN + cg * 4 + j * 16) * 4);
+                        cj = *(const f32x4*)(lds_par + BN * 4 + (wn * WN + cg * 4 + j * 16) * 4);
+                    } else { bj = bias_v[j]; cj = csum_v[j]; }
+                    v = rstd * (v - mu * cj) + bj;
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) d = fmaf(v[r], (float)q[r], d);
+            }
+            d += __shfl_xor(d, 16);
+            d += __shfl_xor(d, 32);
+            part[i] = (p.attn_centred && !p.attn_decoupled) ? rstd * d : d;
+            __builtin_amdgcn_sched_barrier(0);             // one fragment row at a time: the persistent kernels have no registers to spare
         }
-        d += __shfl_xor(d, 16);
-        d += __shfl_xor(d, 32);
-        part[i] = d;
-        __builtin_amdgcn_sched_barrier(0);                 // one fragment row at a time: the persistent kernels have no registers to spare
-    }
+    };
+    if constexpr (LDS_PARAMS) rows(std::integral_constant<int, 2>{});
+    else if (raw) rows(std::integral_constant<int, 1>{});
+    else rows(std::integral_constant<int, 0>{});
     float* red = (float*)smem;                             // [NWN][BM]
     block_sync_lds();                                      // everyone is done with the scratch / K-slab buffers
     if (lane < 16) {
@@ -532,8 +601,32 @@ __device__ __forceinline__ void attn_sum_epilogue(f32x4 (&acc)[WM / 16][WN / 16]
         const float mx = fmaxf(fmaxf(lg[0], lg[1]), fmaxf(lg[2], lg[3]));
         const float e0 = __expf(lg[0] - mx), e1 = __expf(lg[1] - mx), e2 = __expf(lg[2] - mx), e3 = __expf(lg[3] - mx);
         const float den = ((e0 + e1) + e2) + e3;
-        const float pr = (kq == 0 ? e0 : kq == 1 ? e1 : kq == 2 ? e2 : e3) / den;
+        const float ek = kq == 0 ? e0 : kq == 1 ? e1 : kq == 2 ? e2 : e3;
         f32x4 mine = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (p.attn_centred) {
+            // Centred chain (mu = 0): V_row = rstd acc + b, so  O = sum_k (p_k rstd_k) acc_k + b  because sum_k p_k = 1 — one
+            // multiply per element, the bias added ONCE to the fragment the lane keeps.  The quad sum is a REDUCE-SCATTER: lane k
+            // of the quad ends with fragment k's sum (xor 1: fragments of the lane's own parity, xor 2: its own fragment) —
+            // 12 DPP adds per fragment row instead of 32 for four full quad sums of which three were thrown away.
+            // One reciprocal per softmax (v_rcp_f32, 1 ulp) instead of a division per lane.
+            const float sc = ek * (__builtin_amdgcn_rcpf(den) * rstd);
+            const f32x4 w0 = sc * acc[i][0], w1 = sc * acc[i][1], w2 = sc * acc[i][2], w3 = sc * acc[i][3];
+            const bool b0 = (kq & 1) != 0, b1 = (kq & 2) != 0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float sendA = b0 ? w0[r] : w1[r], sendB = b0 ? w2[r] : w3[r];
+                const float a = (b0 ? w1[r] : w0[r])
+                              + __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, sendA), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
+                const float b = (b0 ? w3[r] : w2[r])
+                              + __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, sendB), 0xB1, 0xF, 0xF, true));
+                const float send = b1 ? a : b;
+                mine[r] = (b1 ? b : a)
+                        + __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, send), 0x4E, 0xF, 0xF, true));          // quad_perm [2,3,0,1]
+            }
+            if constexpr (LDS_PARAMS) mine += *(const f32x4*)(lds_par + (wn * WN + cg * 4 + kq * 16) * 4);
+            else mine += kq == 0 ? bias_v[0] : kq == 1 ? bias_v[1] : kq == 2 ? bias_v[2] : bias_v[3];
+        } else {
+        const float pr = ek / den;
 #pragma unroll
         for (int j = 0; j < FN; ++j) {
             f32x4 bj, cj;
@@ -550,6 +643,7 @@ __device__ __forceinline__ void attn_sum_epilogue(f32x4 (&acc)[WM / 16][WN / 16]
                 w[r] = x;
             }
             if (kq == j) mine = w;
+        }
         }
         sat_max = sat_track(sat_track(sat_max, mine[0], mine[1]), mine[2], mine[3]);
 #pragma unroll

@@ -110,8 +110,8 @@ struct GemmArgs {
     const float* stats_in;            // LN_FOLD: per-row (mean, rstd) [M][2]
     // LN_FOLD on the 128-tile kernel (small M: every launch on the critical path counts): instead of (mean, rstd) from a
     // separate ln_finalize launch, the producing GEMM's (mean, M2) slabs [8][M][2] — merged per row by the kernel itself
-    // with ln_merge_slabs(), the very code ln_finalize runs (same bits).  gemm_uses_small_kernel() tells the caller
-    // whether a launch takes that route.
+    // with ln_merge_slabs() — ln_second_moment: the 16 second-moment partials [16][M] with ln_second_moment_rstd() —, the very
+    // code ln_finalize runs (same bits).  gemm_uses_small_kernel() tells the caller whether a launch takes that route.
     const float* stats_parts; long long stats_parts_gs; float ln_inv_dim, ln_eps;
     const float* colsum; float* stats_out;
     const float* acc_init;            // optional fp32 [N]: initial value of the accumulators per output column (a constant row
@@ -135,8 +135,8 @@ struct GemmArgs {
     int parts_k_groups;               // A_parts + groups over K (128-tile kernel): group g covers K-tiles g*K/64 .. of the sources
     int tri;                          // statistics-only launches (NO_STORE): W is UPPER TRIANGULAR (W[n][k] = 0 for k < n): the output
                                       // tile at column n0 starts its K loop at K-tile n0 / 64 (tp_pack_qr.hip)
-    int ln_second_moment;             // stats_parts consumers: the slabs are those of a triangular statistics GEMM — rstd from the
-                                      // second moment (M2 + n mean^2), mean := 0
+    int ln_second_moment;             // stats_parts consumers: not slabs but the 16 second-moment partials [16][M] of a triangular
+                                      // statistics GEMM (kSecondMomentParts, ln_merge_second_moment) -> (0, rstd)
     int* tile_counters;               // persistent kernel: [groups][8] zeroed ints -> dynamic per-XCD tile queue (NULL: static)
     // "TT" mode (tt_rows > 0; tp_gemm8.hip AMODE 3): C[g][M,N] = sum over rows r of group g's range of A[r][m] W[r][n] —
     // both operands K-major, row strides lda_bytes / ldw_bytes; group g covers contraction rows g*K .. g*K + K - 1 of
@@ -183,6 +183,11 @@ struct GemmArgs {
     // of its own (mean, rstd) pairs (ln_finalize_launch(pair_rstd) / attn_kstats_parts put it there — the slot is otherwise 0).
     // The statistics launch and the K launch are then independent and run side by side on two streams (tp_api.hip).
     int attn_decoupled;
+    // attn_centred (the centred chain: every LayerNorm mean of the K/V side is 0, so K = rstd·acc + b and V likewise): the K launch's
+    // logit is rstd · (acc . q) — the bias term is the same for the 4 keys of a region, i.e. softmax-invariant, and is dropped —
+    // and the V launch sums (p·rstd)·acc over the quad and adds the bias once (sum p = 1).  0: the general arithmetic with mean and
+    // colsum (TP_TUNE_TRI_STATS = 1).
+    int attn_centred;
     const float* attn_kstats_parts;   // V launch on the 128-tile kernel merging its producer's slabs (stats_parts): the K group's slabs
     int flags;                        // TP_LINEAR_*
     int groups;
@@ -204,10 +209,8 @@ bool gemm_uses_small_kernel(const GemmArgs& a);        // whether gemm_launch wo
 // M2 = sum of squared deviations from the slab's own mean): Chan's merge in slab order -> (mean, rstd) of nn.LayerNorm
 // (biased variance).  All slabs are fetched before any is used (independent loads in flight).  Used by ln_finalize_kernel
 // and by the 128-tile GEMM's LN-fold prologue: one arithmetic, identical bits.
-// `second_moment`: the slabs describe y = R h + c~ of a triangular statistics GEMM (tp_pack_qr.hip), whose SECOND MOMENT is the
-// variance wanted: M2 + n mean^2 (Chan's merge is exact algebra; every term is a sum of squares) -> (0, rstd).
 template <int NPARTS>
-__device__ __forceinline__ float2 ln_merge_values(const float2 (&st)[NPARTS], float inv_dim, float eps, bool second_moment = false) {
+__device__ __forceinline__ float2 ln_merge_values(const float2 (&st)[NPARTS], float inv_dim, float eps) {
     float s1 = 0.f, q = 0.f, between = 0.f;
 #pragma unroll
     for (int pp = 0; pp < NPARTS; ++pp) { s1 += st[pp].x; q += st[pp].y; }
@@ -215,16 +218,34 @@ __device__ __forceinline__ float2 ln_merge_values(const float2 (&st)[NPARTS], fl
 #pragma unroll
     for (int pp = 0; pp < NPARTS; ++pp) { const float d = st[pp].x - mu; between = fmaf(d, d, between); }
     const float var = (q + 128.0f * between) * inv_dim;         // biased variance (nn.LayerNorm); >= 0 by construction
-    if (second_moment) return make_float2(0.f, 1.0f / sqrtf(fmaf(mu, mu, var) + eps));
     return make_float2(mu, 1.0f / sqrtf(var + eps));
 }
 template <int NPARTS>
-__device__ __forceinline__ float2 ln_merge_slabs(const float* __restrict__ pg, long long M, long long m, float inv_dim, float eps,
-                                                 bool second_moment = false) {
+__device__ __forceinline__ float2 ln_merge_slabs(const float* __restrict__ pg, long long M, long long m, float inv_dim, float eps) {
     float2 st[NPARTS];
 #pragma unroll
     for (int pp = 0; pp < NPARTS; ++pp) st[pp] = *(const float2*)(pg + ((long long)pp * M + m) * 2);
-    return ln_merge_values<NPARTS>(st, inv_dim, eps, second_moment);
+    return ln_merge_values<NPARTS>(st, inv_dim, eps);
+}
+
+// Statistics of a TRIANGULAR statistics GEMM (GemmArgs::tri with TP_LINEAR_NO_STORE — the inference forward's two statistics
+// launches): not (mean, M2) slabs but kSecondMomentParts fp32 partial sums of squares per row, one per 64 output columns,
+// [part][M] (16 x 4 B = the bytes of the 8 float2 slabs: the workspace is the same).  The row's variance on the centred chain IS
+// its second moment / n, so the consumers — ln_finalize_kernel, the 128-tile kernel's in-kernel merge (stats_parts,
+// attn_kstats_parts) — add the partials in ONE fixed order, a balanced tree over the part index, and return (0, rstd).  All
+// loads first (independent, one round trip).  The order does not depend on the kernel that wrote the partials.
+constexpr int kSecondMomentParts = 16;
+__device__ __forceinline__ float ln_second_moment_rstd(const float (&v)[kSecondMomentParts], float inv_dim, float eps) {
+    const float a0 = (v[0] + v[1]) + (v[2] + v[3]), a1 = (v[4] + v[5]) + (v[6] + v[7]);
+    const float a2 = (v[8] + v[9]) + (v[10] + v[11]), a3 = (v[12] + v[13]) + (v[14] + v[15]);
+    const float ss = (a0 + a1) + (a2 + a3);
+    return 1.0f / sqrtf(fmaf(ss, inv_dim, eps));
+}
+__device__ __forceinline__ float2 ln_merge_second_moment(const float* __restrict__ pg, long long M, long long m, float inv_dim, float eps) {
+    float v[kSecondMomentParts];
+#pragma unroll
+    for (int pp = 0; pp < kSecondMomentParts; ++pp) v[pp] = pg[(long long)pp * M + m];
+    return make_float2(0.f, ln_second_moment_rstd(v, inv_dim, eps));
 }
 
 int gemm_pick_tile(int M, int N, int forced, int groups = 1);     // -> 128 or 256

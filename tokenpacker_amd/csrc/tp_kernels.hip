@@ -764,13 +764,15 @@ ln_finalize_kernel(const float* __restrict__ parts, float* __restrict__ mean_rst
     if (m >= M) return;
     const float* pg = parts + (long long)g * nparts * M * 2;
     if constexpr (NPARTS > 0) {
-        float2 r = ln_merge_slabs<NPARTS>(pg, M, m, inv_dim, eps, second_moment);
+        // second_moment (a triangular statistics GEMM's output): 16 partial sums of squares [16][M] instead of 8 (mean, M2) slabs —
+        // the same bytes per group; (0, rstd) by ln_merge_second_moment's fixed order
+        float2 r = second_moment ? ln_merge_second_moment(pg, M, m, inv_dim, eps) : ln_merge_slabs<NPARTS>(pg, M, m, inv_dim, eps);
         // pair_rstd (second-moment statistics only: every mean is 0): the mean slot of group 1 carries group 0's rstd — what the
         // V launch of the decoupled attention epilogues scales the K launch's raw logits with (GemmArgs::attn_decoupled)
-        if (pair_rstd && g == 1) r.x = ln_merge_slabs<NPARTS>(parts, M, m, inv_dim, eps, second_moment).y;
+        if (pair_rstd && g == 1) r.x = ln_merge_second_moment(parts, M, m, inv_dim, eps).y;
         *(float2*)(mean_rstd + ((long long)g * M + m) * 2) = r;
         return;
-    } else {
+    } else {                                               // (generic slab count: (mean, M2) slabs only — the launch rejects second_moment)
         float s1 = 0.f, q = 0.f, between = 0.f, mu;
         for (int pp = 0; pp < nparts; ++pp) {
             const float2 st = *(const float2*)(pg + ((long long)pp * M + m) * 2);
@@ -782,19 +784,20 @@ ln_finalize_kernel(const float* __restrict__ parts, float* __restrict__ mean_rst
             between = fmaf(d, d, between);
         }
         const float var = (q + 128.0f * between) * inv_dim;    // biased variance (nn.LayerNorm); >= 0 by construction
-        *(float2*)(mean_rstd + ((long long)g * M + m) * 2) = second_moment ? make_float2(0.f, 1.0f / sqrtf(fmaf(mu, mu, var) + eps))
-                                                                          : make_float2(mu, 1.0f / sqrtf(var + eps));
+        *(float2*)(mean_rstd + ((long long)g * M + m) * 2) = make_float2(mu, 1.0f / sqrtf(var + eps));
     }
 }
 
 int ln_finalize_launch(const float* parts, float* mean_rstd, long long M, int nparts, int groups, int ln_dim,
                        float eps, hipStream_t stream, bool second_moment, bool pair_rstd) {
     dim3 grid((unsigned)((M + 255) / 256), (unsigned)groups);
+    static_assert(2 * 8 == kSecondMomentParts, "second-moment partials: the bytes of 8 slabs");
+    if (second_moment && nparts != 8) { set_error("ln_finalize: second-moment statistics come as 16 partials (8 slabs' worth)"); return TP_ERR_INVALID_ARG; }
     if (pair_rstd && (nparts != 8 || groups != 2 || !second_moment)) { set_error("ln_finalize: pair_rstd needs 8 slabs, 2 groups, second-moment statistics"); return TP_ERR_INVALID_ARG; }
     if (nparts == 8)
         hipLaunchKernelGGL(ln_finalize_kernel<8>, grid, dim3(256), 0, stream, parts, mean_rstd, M, nparts, 1.0f / ln_dim, eps, second_moment, pair_rstd);
     else
-        hipLaunchKernelGGL(ln_finalize_kernel<0>, grid, dim3(256), 0, stream, parts, mean_rstd, M, nparts, 1.0f / ln_dim, eps, second_moment, false);
+        hipLaunchKernelGGL(ln_finalize_kernel<0>, grid, dim3(256), 0, stream, parts, mean_rstd, M, nparts, 1.0f / ln_dim, eps, false, false);
     return check_launch("ln_finalize_kernel");
 }
 
