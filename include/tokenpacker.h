@@ -737,6 +737,76 @@ int tp_hd_slice_u8(const tp_hd_slice_image* plan_host, const void* plan_dev, int
                    const uint8_t* pixels, int64_t pixel_bytes, const float* lut /* device [3][256] */,
                    void* crops, int64_t n_crops, int block, int out_dtype /* TP_F32 | TP_BF16 | TP_F16 */, void* stream);
 
+/* ---- CLIP preprocessing: the 'pad' and default ('square') image modes from uint8 images, bit-exact to PIL ------------
+ * (An ABI 6 extension, detected by symbol: an older ABI 6 build lacks tp_clip_preprocess.)
+ * What the reference's loader and drivers do to a decoded picture when image_aspect_ratio is not 'slice'
+ * (llava/mm_utils.py:14-37, train.py:679-694, 732-734): optionally expand2square with a background colour, then
+ * CLIPImageProcessor.preprocess — PIL's 8-bit bicubic resize (shortest edge to `size`, or the padded square to size x size),
+ * centre crop to size x size, rescale by 1/255, normalise — and the driver's `.to(dtype)`; for a whole batch of raw RGB
+ * uint8 images of different sizes, as TWO launches, with results that equal the reference's bit for bit.
+ *
+ * Pillow's 8-bit resize is integer arithmetic.  Per axis: int32 coefficients k with 22 fractional bits and, per output
+ * position, the taps [xmin, xmin + xcount); a sample is clip8((2^21 + sum_t k[t] * src[xmin + t]) >> 22) (arithmetic shift,
+ * saturated to 0 .. 255).  The horizontal pass runs first and ROUNDS to uint8, then the vertical one: the intermediate
+ * rounding is part of the result.
+ *
+ * tp_resize_coeffs (host only, no GPU needed) is the single source of the tables: Pillow's precompute_coeffs /
+ * normalize_coeffs_8bpc for the bicubic filter, evaluated in IEEE double in Pillow's order without contraction, for the
+ * output positions [first_out, first_out + n_out) of a resize of in_size to out_size — only the `size` positions inside the
+ * crop window are ever needed, however long the resized side.  *ksize = the taps per position; kk [n_out][ksize] (zero
+ * behind xcount), bounds [n_out][2] = (xmin, xcount).  With kk == bounds == NULL only *ksize is written. */
+int tp_resize_coeffs(int in_size, int out_size, int first_out, int n_out, int32_t* kk, int32_t* bounds, int* ksize);
+
+/* One image of tp_clip_preprocess's plan.  The resize reads a virtual in_h x in_w picture: the stored H x W image itself
+ * (TP_CLIP_SQUARE; in_h = H, in_w = W, pad_top = pad_left = 0) or the square of side max(H, W) filled with `background` in
+ * which the image sits at (pad_top, pad_left) (TP_CLIP_PAD; never materialised).  It is resized to out_h x out_w, of which the
+ * window (crop_top, crop_left) + size x size is the result (tokenpacker_amd.preprocess.preprocess_plan has the reference's
+ * rules).  Tables, as int32 word offsets into `coeffs`, for the `size` positions of the window:
+ *   kk_h [ksize_h][size]  TAP-MAJOR (the transpose of what tp_resize_coeffs writes: adjacent lanes are adjacent columns)
+ *   bounds_h [size][2], kk_v [size][ksize_v], bounds_v [size][2]  as tp_resize_coeffs writes them
+ * The horizontal pass covers the virtual rows [row0, row0 + rows) — every row a vertical tap of the window touches — and
+ * leaves them as uint8 [rows][size][3] at workspace + ws_offset. */
+#define TP_CLIP_SQUARE 0
+#define TP_CLIP_PAD 1
+typedef struct tp_clip_image {
+    int64_t src_offset;            /* byte offset of pixel (0,0) in `pixels` */
+    int64_t ws_offset;             /* byte offset of the image's workspace slice, a multiple of 16 */
+    int32_t H, W, row_stride;      /* row_stride in bytes, >= 3*W */
+    int32_t mode;                  /* TP_CLIP_SQUARE | TP_CLIP_PAD */
+    int32_t in_h, in_w, pad_top, pad_left;
+    int32_t out_h, out_w, crop_top, crop_left;
+    int32_t ksize_h, ksize_v;      /* tp_resize_coeffs' tap counts of in_w -> out_w and in_h -> out_h */
+    int32_t row0, rows;
+    int32_t kk_h, bounds_h, kk_v, bounds_v;
+    uint8_t background[4];         /* R, G, B, 0: what TP_CLIP_PAD reads outside the content */
+    int32_t reserved;
+} tp_clip_image;
+
+/* The workspace a plan needs: the end of its furthest slice (ws_offset + rows * size * 3), rounded up to 16.  Host only.
+ * 0 + tp_last_error() for a plan whose records are invalid. */
+size_t tp_clip_preprocess_workspace_bytes(const tp_clip_image* plan_host, int n_images, int size);
+
+/*   pixels [pixel_bytes]  device bytes; image i is HWC uint8, pixel (y, x) at src_offset + y * row_stride + 3 * x.
+ *                         pixel_bytes >= 4: a pixel is fetched by one 4-byte load, moved down where it would end past the
+ *                         buffer — no address outside pixels[0, pixel_bytes) is ever formed.
+ *   lut [3][256] fp32     device table lut[c][u] = fl(fl(fl(u / 255) - mean_c) / std_c) (tokenpacker_amd.hd.normalisation_table)
+ *   coeffs [coeff_words]  the int32 tables of all images, the same words on the host (validated) and on the device (read)
+ *   workspace             caller-owned device bytes, 16-byte aligned, at least tp_clip_preprocess_workspace_bytes
+ *   out [n_images, 3, size, size] in out_dtype (TP_F32, TP_BF16 or TP_F16; one rounding, Tensor.to's), 16-byte aligned
+ * The plan is the same words on the host (plan_host, read by the validation) and on the device (plan_dev, 8-byte aligned, read
+ * by the kernels).  The call validates on the host first (TP_ERR_INVALID_ARG, each with its own message: NULL or misaligned
+ * pointers; sizes below 1; a side beyond the supported maximum of 16384 pixels — refused, never truncated; a geometry that
+ * does not describe the image; an image outside `pixels`; size not a multiple of 8; tables or workspace slices that overlap
+ * the one before them or fall outside their buffers — both must come in plan order; a tap range outside [0, in_size) or
+ * outside the workspace rows; out_dtype), then only enqueues two launches, whatever n_images: no allocation, no atomics, no
+ * synchronisation, no division and no floating-point arithmetic on the device other than the final rounding.  The kernels
+ * check the device copy of an entry again, write zeros for one that fails and form no address from it. */
+int tp_clip_preprocess(const tp_clip_image* plan_host, const void* plan_dev, int n_images,
+                       const uint8_t* pixels, int64_t pixel_bytes, const float* lut /* device [3][256] */,
+                       const int32_t* coeffs_host, const int32_t* coeffs_dev, int64_t coeff_words,
+                       void* workspace, int64_t workspace_bytes, void* out, int size,
+                       int out_dtype /* TP_F32 | TP_BF16 | TP_F16 */, void* stream);
+
 /* ---- debug: fp16 saturation scan ---------------------------------------------------------------------------------
  * Every activation between the kernels of tp_forward is fp16 and every epilogue CLAMPS to +-65504 instead of producing
  * inf.  After a tp_forward on `stream` with the same desc / workspace, this scans the nine intermediate

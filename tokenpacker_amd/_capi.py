@@ -65,6 +65,7 @@ EXPORTED_SYMBOLS = (
     "tp_hd_assemble_backward_workspace_bytes", "tp_hd_assemble_backward",
     "tp_splice", "tp_splice_backward_workspace_bytes", "tp_splice_backward",
     "tp_desc_known_flags", "tp_hd_slice_u8",
+    "tp_resize_coeffs", "tp_clip_preprocess_workspace_bytes", "tp_clip_preprocess",
     "tp_tuning_create", "tp_tuning_destroy", "tp_tuning_set", "tp_tuning_get", "tp_gather_alloc_flags", "tp_gather_free_flags", "tp_gather_export", "tp_gather_open", "tp_gather_close", "tp_gather_push", "tp_gather_sync",
 )
 # include/tokenpacker_test.h: the stateless test hooks — libtokenpacker_exp.so only (load_test_library()), never the product library
@@ -174,6 +175,20 @@ class tp_hd_slice_image(Structure):
     _fields_ = [("src_offset", c_int64), ("H", c_int32), ("W", c_int32), ("row_stride", c_int32),
                 ("h_block", c_int32), ("w_block", c_int32), ("h_res", c_int32), ("w_res", c_int32), ("hg", c_int32), ("wg", c_int32),
                 ("first_crop", c_int32)]
+
+
+TP_CLIP_SQUARE, TP_CLIP_PAD = 0, 1
+
+
+class tp_clip_image(Structure):
+    """One image of tp_clip_preprocess's plan (include/tokenpacker.h, "CLIP preprocessing"): where its HWC uint8 bytes lie,
+    preprocess.preprocess_plan's geometry, its coefficient tables (int32 word offsets) and its workspace slice."""
+    _fields_ = [("src_offset", c_int64), ("ws_offset", c_int64), ("H", c_int32), ("W", c_int32), ("row_stride", c_int32),
+                ("mode", c_int32), ("in_h", c_int32), ("in_w", c_int32), ("pad_top", c_int32), ("pad_left", c_int32),
+                ("out_h", c_int32), ("out_w", c_int32), ("crop_top", c_int32), ("crop_left", c_int32),
+                ("ksize_h", c_int32), ("ksize_v", c_int32), ("row0", c_int32), ("rows", c_int32),
+                ("kk_h", c_int32), ("bounds_h", c_int32), ("kk_v", c_int32), ("bounds_v", c_int32),
+                ("background", ctypes.c_uint8 * 4), ("reserved", c_int32)]
 
 
 TP_SPLICE_TEXT, TP_SPLICE_LITERAL, TP_SPLICE_FEATURE, TP_SPLICE_PAD = 0, 1, 2, 3
@@ -367,6 +382,15 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.tp_hd_slice_u8.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int,
                                        c_void_p]
 
+    if hasattr(lib, "tp_clip_preprocess"):               # (an ABI 6 extension — clip_preprocess_supported())
+        lib.tp_resize_coeffs.restype = c_int
+        lib.tp_resize_coeffs.argtypes = [c_int, c_int, c_int, c_int, c_void_p, c_void_p, POINTER(c_int)]
+        lib.tp_clip_preprocess_workspace_bytes.restype = c_size_t
+        lib.tp_clip_preprocess_workspace_bytes.argtypes = [c_void_p, c_int, c_int]
+        lib.tp_clip_preprocess.restype = c_int
+        lib.tp_clip_preprocess.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                           c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p]
+
     if lib.tp_version() != TP_ABI_VERSION:
         raise TokenPackerLibraryError(
             f"{path}: ABI version {lib.tp_version()} != expected {TP_ABI_VERSION}; rebuild the library")
@@ -476,6 +500,13 @@ def hd_slice_u8_supported() -> bool:
     return hasattr(load_library(), "tp_hd_slice_u8")
 
 
+def clip_preprocess_supported() -> bool:
+    """Whether the loaded library has the CLIP preprocessing of the pad / square image modes (``tp_resize_coeffs``,
+    ``tp_clip_preprocess``): detected by symbol, an older ABI 6 build lacks them."""
+    lib = load_library()
+    return hasattr(lib, "tp_clip_preprocess") and hasattr(lib, "tp_resize_coeffs") and hasattr(lib, "tp_clip_preprocess_workspace_bytes")
+
+
 def make_desc(batch: int, raw_grid: int, scale_factor: int, hidden_size: int, dtype: int,
               out_dtype: int | None = None, ln_eps: float = 1e-6, flags: int = 0, tuning=None) -> tp_desc:
     """`tuning`: a TuningContext (or its raw handle) the call reads its knobs from; None = the process-wide table."""
@@ -561,5 +592,5 @@ def get_tuning(key: int) -> int:
 
 
 __all__ = [n for n in dir() if n.startswith(("TP_", "tp_"))] + [
-    "load_library", "load_test_library", "last_error", "check", "make_desc", "strides3", "backward_plan", "raw_f32_supported", "sharded_optim_supported", "hd_slice_u8_supported", "BWD_STAGE_NAMES", "set_tuning", "get_tuning", "TuningContext",
+    "load_library", "load_test_library", "last_error", "check", "make_desc", "strides3", "backward_plan", "raw_f32_supported", "sharded_optim_supported", "hd_slice_u8_supported", "clip_preprocess_supported", "BWD_STAGE_NAMES", "set_tuning", "get_tuning", "TuningContext",
     "TokenPackerLibraryError", "WEIGHT_FIELDS", "EXPORTED_SYMBOLS", "TEST_SYMBOLS", "LIB_PATH", "EXP_LIB_PATH", "byref"]
