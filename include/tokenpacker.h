@@ -402,8 +402,19 @@ int tp_backward_inputs_parts(const tp_desc* desc, const void* const xm_parts[4],
  *   grad   NULL, or fp32 in the mask's layout: dL/dmask_j = p_j (dP_j - D) summed over whatever shares entry j (mode 1: every
  *          image, query and head; mode 2: nothing — each entry is written once).  Unscaled: the fp16 gradient chain's dynamic
  *          scale is taken out on the device.  Deterministic (mode 1 sums per-query partials in a fixed order), no atomics.
- * A fully masked row (every key of some head at -inf) gives a non-finite output, as in the reference, and non-finite
- * gradients.  A per-head mask (mode 2) needs the whole batch in one launch, as in inference.
+ * -inf may sit at ANY key position, the leading keys included, as long as one key of the row (one head of one query) is finite:
+ * every attention kernel, forward and backward, then gives the reference's softmax (tests/test_gpu_attention_masks.py).
+ * A FULLY masked row (every key of some head of some query at -inf) is NOT the reference's NaN row.  The attention itself gives NaN
+ * for that head (128 elements of O; under the absorbed schedule the head's u, and -65504 in O behind the per-head V GEMM), but every
+ * fp16 GEMM epilogue behind it clamps to +-65504 and a clamp turns NaN into -65504 without setting that stage's status bit.  So the
+ * query's OUTPUT ROW IS FINITE IN EVERY ELEMENT AND MEANINGLESS; the first stage whose finite result then leaves fp16's range sets
+ * its status bit (mlp0_gelu at hidden_size 256), which is how a caller notices: the status word / tp_debug_count_saturated (O: 128
+ * elements, then whole rows of A1 / A2).  In training (bf16 model) dL/dmask of that row is NaN in every element, the gradient of
+ * out_proj.weight is NaN in the head's 128 input columns, every other parameter gradient and the query's dx / dx_multi / other
+ * dmask rows are finite and meaningless, and tp_backward's status word has bits 0 and 2 set.  Every OTHER output row, dx / dx_multi
+ * outside that query's region and the dmask rows of other queries keep their bits (tests/test_gpu_mask_train.py::
+ * test_fully_masked_row).  A caller that can produce such rows must test for them itself.
+ * A per-head mask (mode 2) needs the whole batch in one launch, as in inference.
  *   tp_forward_train_masked  xm_parts NULL: x_multi concatenated (xm_strides its strides); non-NULL: the four sources of
  *                            tp_forward_train_parts (xm_strides their common strides; x_multi ignored)
  *   tp_forward_parts_masked  inference: tp_forward_parts with a mask (workspace sized with TP_DESC_MASKED)

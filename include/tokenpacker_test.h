@@ -34,6 +34,21 @@ int tp_test_pack_qr(const void* w2_f16, const float* b2, void* r_f16, float* c_t
  * tests/test_gpu_pack_image.py slices the image with it. */
 int tp_test_packed_layout(int hidden_size, const char* name, size_t* offset, size_t* bytes);
 
+/* ---- test hooks: the FORWARD's two attention kernels one at a time, WITH the additive mask the public tp_region_attention /
+ * tp_region_attention_absorbed do not take (tests/test_gpu_attention_masks.py).  Pass-throughs to the launchers tp_forward* calls
+ * (csrc/tp_internal.h: region_attention_launch, region_attention_absorbed_launch), after the host checks described below: NULL
+ * pointers, 16-byte alignment (mr_k / mr_v: 8, mask: 4), B > 0, s dividing grid <= 1024, mask_mode 0 (mask NULL) / 1 / 2 (mask given).
+ * mask: fp32, mode 1 [s*s], mode 2 [(M B) 8, s*s] with batch index region * B + image; -inf allowed at any key position as long as
+ * one key of the row stays finite. */
+/* o [B M, 1024] = softmax(q k^T / sqrt(128) + mask) v per head, fp16; q [B M, 1024], k / v [B grid^2, 1024] in raster order
+ * (region_major 0) or with the rows of region m at m * s*s + key inside each image (region_major 1). */
+int tp_test_region_attention(const void* q, const void* k, const void* v, void* o, int B, int grid, int s, const float* mask,
+                             int mask_mode, int region_major, void* stream);
+/* The absorbed schedule's attention in its plain (not RAW) form: qt [B M, 8, 1024] fp16, h2k / h2v [B grid^2, 1024] fp16 with their
+ * per-row (mean, rstd) mr_k / mr_v (fp32 [B grid^2][2]) -> u [B M, 8, 1024] fp16.  s*s > 64: the launcher's TP_ERR_INVALID_ARG. */
+int tp_test_region_attention_absorbed(const void* qt, const void* h2k, const void* h2v, const float* mr_k, const float* mr_v, void* u,
+                                      int B, int grid, int s, const float* mask, int mask_mode, void* stream);
+
 /* ---- test hooks: the BACKWARD's kernels one at a time (tests/test_gpu_bwd_kernels.py compares each with fp64 math on the same
  * rounded operands, tests/bwd_ref.py).  Each is a pass-through to the launcher tp_backward itself calls (csrc/tp_internal.h:
  * bw_*_launch, point_queries_bwd_launch, gemm_launch): same objects, same kernels.  Every hook checks on the HOST what its launcher

@@ -263,7 +263,7 @@ LN_FAMILIES = ("plain", "mean40", "tinyvar", "mixed")
 LN_FULL_CASES = ((18432, "mixed"), (18432, "mean40"), (147456, "plain"), (147456, "tinyvar"))    # (rows, family): bf16, every LN_NBLOCKS
 ATTN_CASES = ((24, 1, 2), (24, 2, 3), (24, 3, 1), (24, 4, 3), (24, 6, 2), (24, 8, 1), (24, 8, 3), (24, 12, 3), (16, 4, 1),
               (8, 2, 5))                        # (grid, s, B): s = 8 has 9 queries per image — B M % 4 != 0 twice
-ATTN_VARIANTS = ("plain", "peaked", "mask1", "mask2", "mask1_neg", "mask2_inf")
+ATTN_VARIANTS = ("plain", "peaked", "mask1", "mask2", "mask1_neg", "mask2_inf", "mask1_lead", "mask2_lead")
 PQ_CASES = tuple((24, s) for s in (1, 2, 3, 4, 6)) + ((16, 4), (8, 2))
 COLSUM_CASES = tuple((R, C, C) for R in (1, 63, 64, 65, 100, 4097) for C in (8, 520, 1024)) + (
     (100, 2048, 4096), (4097, 4096, 4096), (18432, 2048, 4096), (18432, 4096, 4096), (147456, 1024, 2048), (147456, 8, 8))   # (R, C, ld)
@@ -308,7 +308,8 @@ def ln_inputs(family: str, rows: int, gdtype, seed: int, device="cpu", ln_eps: f
 
 
 def attn_inputs(grid: int, s: int, B: int, gdtype, variant: str, seed: int, device="cpu"):
-    """(q, k, v, dout, mask, mode) of one attention-backward case.  Masks never mask a whole row."""
+    """(q, k, v, dout, mask, mode) of one attention-backward case.  Masks never mask a whole row; the `_neg` / `_inf` variants keep
+    key 0 visible, the `_lead` variants mask the leading keys and keep the later ones."""
     g = _gen(seed, device)
     M, N, S2 = (grid // s) ** 2, grid * grid, s * s
     q = torch.randn(B, M, E, generator=g, device=device) * (6.0 if variant == "peaked" else 1.0)
@@ -326,6 +327,11 @@ def attn_inputs(grid: int, s: int, B: int, gdtype, variant: str, seed: int, devi
             mask[hit] = -1e4 if variant.endswith("_neg") else float("-inf")
             if mode == 1:
                 mask[0, S2 - 1] = -1e4 if variant.endswith("_neg") else float("-inf")
+        if S2 > 1 and variant.endswith("_lead"):                            # -inf on the LEADING keys 0..3 (mode 2: 0..3 | 0..4 by row)
+            lead = torch.full((rows,), 4, device=device)
+            lead[1::2] = 5
+            lead = lead.clamp(max=S2 - 1)                                   # (at least the last key stays: no fully masked row)
+            mask[torch.arange(S2, device=device)[None, :] < lead[:, None]] = float("-inf")
         mask = mask.reshape(S2) if mode == 1 else mask
     return q.half(), k.half(), v.half(), dout.to(gdtype), mask, mode
 

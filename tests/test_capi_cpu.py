@@ -325,7 +325,7 @@ def test_tp_linear_refuses_the_training_flags():
 
 
 def test_backward_kernel_hooks_refuse_bad_arguments():
-    """Every tp_test_bw_* / tp_test_point_queries_bwd / tp_test_linear_bwd hook turns a mistaken call — NULL, misaligned, a count
+    """Every tp_test_bw_* / tp_test_region_attention* / tp_test_point_queries_bwd / tp_test_linear_bwd hook turns a mistaken call — NULL, misaligned, a count
     that is not a multiple of 8 / 4, a scratch too small — into TP_ERR_INVALID_ARG on the host (include/tokenpacker_test.h)."""
     tl = _capi.load_test_library()
     E = _capi.TP_ERR_INVALID_ARG
@@ -384,6 +384,16 @@ def test_backward_kernel_hooks_refuse_bad_arguments():
                                                                                  (12, 1), (12, 2)])
     good = [BF16, p, p, p, p, p, p, p, 2, 24, 3, p, 1, p, None, p, 2 * 64 * 12 * 4, p, 32 * 12, None, None]
     refused(tl.tp_test_bw_region_attention, good, [(15, None), (17, None), (15, odd), (13, odd), (16, 2 * 64 * 12 * 4 - 1), (18, 32 * 12 - 1)])
+    # (q, k, v, o, B, grid, s, mask, mask_mode, region_major, stream)
+    refused(tl.tp_test_region_attention, [p, p, p, p, 2, 24, 3, None, 0, 0, None],
+            [(i, None) for i in range(4)] + [(i, odd) for i in range(4)] + [(4, 0), (5, 0), (6, 5), (6, 0), (5, 2048), (7, p), (8, 1), (8, 2), (8, 3),
+                                                                           (8, -1), (9, 2), (9, -1)])
+    refused(tl.tp_test_region_attention, [p, p, p, p, 2, 24, 3, p, 2, 1, None], [(7, None), (7, p + 2), (8, 0)])
+    # (qt, h2k, h2v, mr_k, mr_v, u, B, grid, s, mask, mask_mode, stream)
+    refused(tl.tp_test_region_attention_absorbed, [p, p, p, p, p, p, 2, 24, 3, None, 0, None],
+            [(i, None) for i in range(6)] + [(i, odd) for i in (0, 1, 2, 5)] + [(3, p + 4), (4, p + 4), (6, 0), (8, 5), (8, 0), (9, p), (10, 1), (10, 3)])
+    assert tl.tp_test_region_attention_absorbed(p, p, p, p, p, p, 1, 18, 9, None, 0, None) == E       # (the launcher's refusal: 81 keys)
+    assert "keys > 64" in tl.tp_last_error().decode()
     # (dtype, dq0, inv_scale, dx, B, grid, s, stream)
     refused(tl.tp_test_point_queries_bwd, [F16, p, None, p, 1, 24, 2, None], [(1, None), (3, None), (1, odd), (3, odd), (0, F32), (4, 0), (6, 5), (6, 0)])
     # (M, N, K, dtype, out_dtype, flags, A, lda, W, C, ldc, Z, ldz, out_scale, tile, stream)

@@ -472,6 +472,32 @@ def test_attn_mask_is_honoured(s, dtype):
             assert orc.rel_err(y, torch.from_numpy(z[key])) < (3e-2 if dtype == torch.bfloat16 else 4e-3), key   # vs the REAL reference
 
 
+@pytest.mark.parametrize("s", [3, 4, 12])
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+def test_attn_mask_with_inf_at_any_key_position(s, dtype):
+    """Masks that do NOT keep key 0 visible (tests/mask_patterns.py): the 3-D boolean random pattern — every row's visible key
+    anywhere, rows with the whole leading key group masked planted — and the 2-D float `top_row` (-inf on keys 0 .. s-1), against the
+    fp64 oracle at test_attn_mask_is_honoured's gate.  s = 3, 4 run the absorbed attention kernel, s = 12 the plain one."""
+    from tests import mask_patterns as mp
+    D, B = 256, 2
+    params = synth.make_params(73, D)
+    x, xm = synth.make_inputs(173, B, dtype)
+    m = _module(params, s, D, dtype)
+    m.output_fp32 = True
+    p_lp = {k: v.to(dtype) for k, v in params.items()}
+    with torch.no_grad():
+        y0 = m((x.cuda(), xm.cuda()))
+        for mask in (mp.mode2_bool(24, s, B), mp.top_row_2d(s)):
+            y = m((x.cuda(), xm.cuda()), attn_mask=mask)
+            assert bool(torch.isfinite(y).all()), (tuple(mask.shape), int((~torch.isfinite(y)).sum()))
+            y_exact = orc.forward(p_lp, x, xm, scale_factor=s, compute_dtype=torch.float64, io_dtype=dtype, attn_mask=mask)
+            e = orc.rel_err(y, y_exact)
+            print(f"\n[parity] inf-anywhere mask s={s} {dtype} {tuple(mask.shape)}: rel_err {e:.3e}")
+            assert e <= 1.2e-3, (tuple(mask.shape), mask.dtype, e)
+            assert float((y - y0).abs().max()) > 0.05          # the mask changes the result
+            assert sum(m.saturation_report().values()) == 0
+
+
 @pytest.mark.parametrize("grid,s", [(24, 1), (24, 6), (24, 8), (24, 12), (24, 24), (16, 4), (12, 3), (8, 2), (16, 2), (12, 2), (6, 2)])
 def test_whole_path_other_scale_factors_and_grids(grid, s):
     """Every scale factor dividing the grid, on every schedule: s = 1, 2 plain (fused LayerNorm chain), s = 3 … 8 absorbed

@@ -148,6 +148,137 @@ def test_gradients_with_a_mask_vs_oracle_and_the_reference(path, dtype, kind):
     assert e <= bar, (e, bar)
 
 
+@pytest.mark.parametrize("s", [3, 4])
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("kind", ["2d_float", "3d_bool"])
+def test_training_with_inf_at_any_key_position(s, dtype, kind):
+    """Masks that do NOT keep key 0 visible (tests/mask_patterns.py: the 2-D float `top_row`, -inf on keys 0 .. s-1 — at s = 4 the
+    plain kernel's whole first key group; the 3-D boolean random pattern with its planted rows), on the weights and inputs of
+    tests/golden/mask_grad_s*.npz: the training forward is the inference forward of the same schedule bit for bit; parameter
+    gradients and dmask at the metrics and gates of test_gradients_with_a_mask_vs_oracle_and_the_reference, input gradients at
+    test_input_gradients_with_a_mask's; dmask is exactly 0 where the mask is -inf."""
+    from tests import gpu_util as gu, mask_patterns as mp
+    z = np.load(os.path.join(os.path.dirname(__file__), "golden", f"mask_grad_s{s}.npz"))
+    D, B, iseed = int(z["hidden_size"]), int(z["batch"]), int(z["input_seed"])
+    assert (int(z["scale_factor"]), D, B) == (s, 256, 2)
+    names = [str(n) for n in z["names"]]
+    params = synth.make_params(int(z["param_seed"]), D)
+    x, xm = synth.make_inputs(iseed, B)
+    x, xm = x.to(dtype), xm.to(dtype)
+    w = torch.randn(B, (24 // s) ** 2, D, generator=torch.Generator().manual_seed(iseed + 1000))
+    mask = _leaf(mp.top_row_2d(s) if kind == "2d_float" else mp.mode2_bool(24, s, B), device="cuda")
+    m = _module(params, D, s, dtype)
+    m.input_gradients = True
+    y, got, dmask, dx, dxm = _step(m, x, xm, w, mask, inputs=True)
+    assert bool(torch.isfinite(y).all()), int((~torch.isfinite(y)).sum())
+    with torch.no_grad(), gu.training_schedule_for_inference():
+        y_inf = m((x.cuda(), xm.cuda()), attn_mask=mask.detach())
+    assert torch.equal(y, y_inf)
+    want, want_dmask, want_dx, want_dxm = _oracle(params, x, xm, w, s, dtype, mask, inputs=True)
+    errs = synth.grad_errors({k: v.double().cpu() for k, v in got.items()}, want)
+    tag = "bf16" if dtype == torch.bfloat16 else "fp16"
+    ref_own = dict(zip(names, z[f"ref_{tag}_grad_{kind}"].tolist()))
+    e_dx, e_dxm = _rel_l2(dx, want_dx), _rel_l2(dxm, want_dxm)
+    line = (f"\n[mask-grad] inf-anywhere s={s} {tag} {kind}: params worst {max(errs.values()):.3e} (reference's own "
+            f"{max(ref_own.values()):.3e}); dx {e_dx:.3e}, dx_multi {e_dxm:.3e}")
+    e = bar = 0.0
+    if kind == "2d_float":
+        assert dmask is not None and dmask.dtype == mask.dtype and dmask.shape == mask.shape and dmask.device == mask.device
+        assert float(dmask[torch.isinf(mask.detach())].abs().max()) == 0.0              # exactly 0 at the -inf entries
+        e, bar = _rel_l2(dmask, want_dmask), float(z[f"ref_{tag}_dmask_{kind}"])
+        line += f"; dmask {e:.3e} (reference's own {bar:.3e})"
+    print(line)
+    for k in names:
+        assert errs[k] <= GATE_L2, (k, errs[k])
+        assert errs[k] <= 1.5 * ref_own[k] + 1e-4, (k, errs[k], ref_own[k])
+    assert e <= bar, (e, bar)
+    assert e_dx <= GATE_L2 and e_dxm <= GATE_L2, (e_dx, e_dxm)
+
+
+def _masked_row_runs(s, dtype, h_star):
+    """One head (h_star) of one query fully masked in a 3-D float mask, against the same run with that mask row at zero (every other
+    row is zero in both): inference and one training step each -> (geometry, inference pair, training pair)."""
+    from tests import gpu_util as gu
+    D, B = 256, 2
+    G = 24 // s
+    M, S2 = G * G, s * s
+    b_star, m_star = 1, G + 2                                             # image 1, region (1, 2)
+    params, x, xm, w = _inputs(490 + s, B, s, D, dtype)
+    m = _module(params, D, s, dtype)
+    m.input_gradients = True
+    row = (m_star * B + b_star) * 8 + h_star
+    runs = []
+    for fill in (float("-inf"), 0.0):
+        raw = torch.zeros(M * B * 8, 1, S2)
+        raw[row] = fill
+        with torch.no_grad():
+            y_inf = m((x.cuda(), xm.cuda()), attn_mask=raw.cuda())
+            sat, rep = m.saturated_stages(clear=True), m.saturation_report()
+            with gu.training_schedule_for_inference():
+                y_plain = m((x.cuda(), xm.cuda()), attn_mask=raw.cuda())      # (the plain attention kernel at every s)
+                sat_plain, rep_plain = m.saturated_stages(clear=True), m.saturation_report()
+        step = _step(m, x, xm, w, _leaf(raw, device="cuda"), inputs=True)
+        runs.append({"y_inf": y_inf, "sat": sat, "rep": rep, "y_plain": y_plain, "sat_plain": sat_plain, "rep_plain": rep_plain,
+                     "step": step, "bwd_sat": m.backward_saturated()})
+    return (B, G, M, S2, b_star, m_star, row), runs[0], runs[1]
+
+
+@pytest.mark.parametrize("s", [2, 3])
+def test_fully_masked_row(s):
+    """A mode-2 mask that fully masks exactly ONE head of ONE query (every key at -inf), in inference on the plain (s = 2, and the
+    training schedule at s = 3) and the absorbed (s = 3) attention kernel and in a training step: every OTHER output row, and every
+    gradient slice that depends on other rows only (dx and dx_multi outside that query's region, dmask rows of other queries),
+    is bit-identical to the run with that one mask row at zero.  The row itself: what include/tokenpacker.h states, pinned below."""
+    dtype, h_star = torch.bfloat16, 5
+    (B, G, M, S2, b_star, m_star, row), bad, good = _masked_row_runs(s, dtype, h_star)
+    others = torch.ones(B, M, dtype=torch.bool)
+    others[b_star, m_star] = False
+    for key in ("y_inf", "y_plain"):
+        assert torch.equal(bad[key][others.cuda()], good[key][others.cuda()]), key
+    yb, _, dmb, dxb, dxmb = bad["step"]
+    yg, _, dmg, dxg, dxmg = good["step"]
+    assert torch.equal(yb[others.cuda()], yg[others.cuda()])
+    assert torch.equal(yb, bad["y_plain"]) and torch.equal(yg, good["y_plain"])       # training forward = inference, that schedule
+    tokens = torch.ones(B, 24, 24, dtype=torch.bool)                                   # the tokens of OTHER regions
+    i, j = divmod(m_star, G)
+    tokens[b_star, i * s:(i + 1) * s, j * s:(j + 1) * s] = False
+    tokens = tokens.reshape(B, 576).cuda()
+    assert torch.equal(dxb[tokens], dxg[tokens]) and torch.equal(dxmb[tokens], dxmg[tokens])
+    rows = torch.ones(M * B * 8, dtype=torch.bool)
+    rows[(m_star * B + b_star) * 8:(m_star * B + b_star + 1) * 8] = False
+    assert torch.equal(dmb[rows.cuda()], dmg[rows.cuda()])
+    assert bool(torch.isfinite(yg).all()) and good["sat"] == () and good["bwd_sat"] == 0
+    _pin_fully_masked_row(s, h_star, bad, good, b_star, m_star, row, tokens, rows)
+
+
+def _pin_fully_masked_row(s, h_star, bad, good, b_star, m_star, row, tokens, rows):
+    """What include/tokenpacker.h says comes out for the fully masked row (bf16 model, D = 256) — NOT the reference's NaN row."""
+    yb, gb, dmb, dxb, dxmb = bad["step"]
+    # the attention's NaN is clamped to -65504 by the fp16 epilogues behind it: the output row is finite in every element ...
+    for y in (bad["y_inf"], bad["y_plain"], yb):
+        assert bool(torch.isfinite(y[b_star, m_star]).all())
+    # ... and the forward's status word names the first stage that then left fp16's range; the scan finds the head's 128 elements of O
+    for sat, rep in ((bad["sat"], bad["rep"]), (bad["sat_plain"], bad["rep_plain"])):
+        assert sat == ("mlp0_gelu",), sat
+        assert rep["O"] == 128 and rep["A2"] > 0 and rep["q0"] == rep["Hkv"] == rep["H2"] == rep["Q1pre"] == rep["Q"] == 0, rep
+    assert bad["rep_plain"]["A1"] == 1024 and bad["rep_plain"]["KV"] == 0
+    # training: dmask of the row is NaN in every element, the query's other heads are finite; out_proj.weight's gradient is NaN in
+    # the head's 128 input columns and nowhere else; every other gradient is finite; the backward's status has bits 0 and 2
+    assert bool(torch.isnan(dmb[row]).all()) and int((~torch.isfinite(dmb[~rows])).sum()) == dmb[row].numel()
+    assert bool(torch.isfinite(dxb).all()) and bool(torch.isfinite(dxmb).all())
+    for k, g in gb.items():
+        if k == "clip_attn.out_proj.weight":
+            cols = torch.zeros(1024, dtype=torch.bool, device=g.device)
+            cols[h_star * 128:(h_star + 1) * 128] = True
+            assert bool(torch.isnan(g[:, cols]).all()) and bool(torch.isfinite(g[:, ~cols]).all())
+        else:
+            assert bool(torch.isfinite(g).all()), k
+    assert torch.equal(gb["mlp.2.bias"], good["step"][1]["mlp.2.bias"])                  # (colsum(dy): no activation in it)
+    assert bad["bwd_sat"] & 5 == 5, bad["bwd_sat"]
+    print(f"\n[masked-row] s={s}: saturated_stages {bad['sat']}, scan {bad['rep']}; plain schedule {bad['rep_plain']}; "
+          f"backward status {bad['bwd_sat']:#x}; max |y| of the row {float(yb[b_star, m_star].float().abs().max()):.3g}")
+
+
 def test_bf16_mask_leaf_gets_a_bf16_gradient():
     """A bf16 2-D leaf on the device: dmask is bf16, its shape, on its device, against the oracle within the reference's own
     bf16 dmask error."""

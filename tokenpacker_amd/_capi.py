@@ -74,7 +74,9 @@ TEST_SYMBOLS = ("tp_test_occupy_cus", "tp_test_pair_occupancy", "tp_test_gemm_ro
                 # the backward's kernels one at a time (tests/test_gpu_bwd_kernels.py)
                 "tp_test_bw_transpose", "tp_test_bw_transpose_batch", "tp_test_bw_colsum_rows", "tp_test_bw_reduce_parts",
                 "tp_test_bw_reduce_many_parts", "tp_test_bw_dynamic_scale", "tp_test_bw_scale_cast", "tp_test_bw_ln_backward",
-                "tp_test_bw_region_attention", "tp_test_point_queries_bwd", "tp_test_linear_bwd")
+                "tp_test_bw_region_attention", "tp_test_point_queries_bwd", "tp_test_linear_bwd",
+                # the forward's two attention kernels with a mask (tests/test_gpu_attention_masks.py)
+                "tp_test_region_attention", "tp_test_region_attention_absorbed")
 TP_COUNTER_SIDE_STREAMS, TP_COUNTER_PAIR_LAUNCHES = 0, 1
 EXP_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtokenpacker_exp.so")
 
@@ -439,6 +441,8 @@ def load_test_library(path: str = EXP_LIB_PATH) -> ctypes.CDLL:
             ("tp_test_bw_ln_backward", [c_int, v, v, v, v, v, v, c_size_t, c_int, c_int64, v, v, v, v]),
             ("tp_test_bw_region_attention", [c_int, v, v, v, v, v, v, v, c_int, c_int, c_int, v, c_int, v, v, v, c_size_t, v, c_size_t, v, v]),
             ("tp_test_point_queries_bwd", [c_int, v, v, v, c_int, c_int, c_int, v]),
+            ("tp_test_region_attention", [v, v, v, v, c_int, c_int, c_int, v, c_int, c_int, v]),
+            ("tp_test_region_attention_absorbed", [v, v, v, v, v, v, c_int, c_int, c_int, v, c_int, v]),
             ("tp_test_linear_bwd", [c_int, c_int, c_int, c_int, c_int, c_int, v, c_int64, v, v, c_int64, v, c_int64, v, c_int, v])):
         fn = getattr(lib, name)
         fn.restype = c_int

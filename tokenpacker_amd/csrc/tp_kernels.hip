@@ -209,7 +209,11 @@ region_attention_kernel(const T* __restrict__ q, const T* __restrict__ k, const 
         for (int u = 0; u < KU; ++u) {
             if (k0 + u < S2) { gmax_a = fmaxf(gmax_a, la[u]); gmax_b = fmaxf(gmax_b, lb[u]); }
         }
-        const float resc_a = __expf(run_max_a - gmax_a), resc_b = __expf(run_max_b - gmax_b);  // exp(-inf)=0 first time
+        // A maximum that is still -inf (attn_mask: every key so far at -inf) is not subtracted — -inf - -inf is NaN, and it would stay
+        // in den and acc for the rest of the row: against 0 such a group weighs exp(-inf) = 0 and rescales nothing.  A finite maximum
+        // is subtracted as ever (the first finite one rescales by exp(-inf) = 0), so those rows keep their bits.
+        const float base_a = gmax_a == -INFINITY ? 0.f : gmax_a, base_b = gmax_b == -INFINITY ? 0.f : gmax_b;
+        const float resc_a = __expf(run_max_a - base_a), resc_b = __expf(run_max_b - base_b);
         den_a *= resc_a; den_b *= resc_b;
 #pragma unroll
         for (int e = 0; e < 8; ++e) { acc_a[e] *= resc_a; acc_b[e] *= resc_b; }
@@ -217,7 +221,7 @@ region_attention_kernel(const T* __restrict__ q, const T* __restrict__ k, const 
 #pragma unroll
         for (int u = 0; u < KU; ++u) {
             if (k0 + u < S2) {
-                const float pa = __expf(la[u] - run_max_a), pb = __expf(lb[u] - run_max_b);
+                const float pa = __expf(la[u] - base_a), pb = __expf(lb[u] - base_b);
                 den_a += pa; den_b += pb;
                 float va[8], vbv[8];
                 load8(vb + row[u] + ea, va);

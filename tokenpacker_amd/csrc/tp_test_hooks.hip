@@ -63,6 +63,34 @@ int tp_test_packed_layout(int hidden_size, const char* name, size_t* offset, siz
     return TP_ERR_INVALID_ARG;
 }
 
+// ---- the forward's two attention kernels (tp_internal.h: region_attention_launch, region_attention_absorbed_launch) --------------
+
+static int attention_geometry(const char* who, int B, int grid, int s, const float* mask, int mask_mode) {
+    if (!(B > 0 && grid > 0 && s > 0 && grid % s == 0 && grid <= 1024)) { set_error("%s: need B > 0 and s dividing grid <= 1024", who); return TP_ERR_INVALID_ARG; }
+    if (!(mask_mode >= 0 && mask_mode <= 2)) { set_error("%s: mask_mode 0 / 1 / 2", who); return TP_ERR_INVALID_ARG; }
+    if ((mask_mode == 0) != (mask == nullptr)) { set_error("%s: mask_mode 0 takes no mask, mask_mode 1 / 2 needs one", who); return TP_ERR_INVALID_ARG; }
+    if ((uintptr_t)mask & 3) { set_error("%s: the mask must be 4-byte aligned", who); return TP_ERR_INVALID_ARG; }
+    return TP_OK;
+}
+
+int tp_test_region_attention(const void* q, const void* k, const void* v, void* o, int B, int grid, int s, const float* mask,
+                             int mask_mode, int region_major, void* stream) {
+    TP_REQUIRE(q && k && v && o, "tp_test_region_attention: NULL argument");
+    TP_REQUIRE(al16(q) && al16(k) && al16(v) && al16(o), "tp_test_region_attention: q / k / v / o must be 16-byte aligned");
+    TP_TRY(attention_geometry("tp_test_region_attention", B, grid, s, mask, mask_mode));
+    TP_REQUIRE(region_major == 0 || region_major == 1, "tp_test_region_attention: region_major 0 / 1");
+    return region_attention_launch(q, k, v, o, B, grid, s, (hipStream_t)stream, mask, mask_mode, region_major);
+}
+
+int tp_test_region_attention_absorbed(const void* qt, const void* h2k, const void* h2v, const float* mr_k, const float* mr_v, void* u,
+                                      int B, int grid, int s, const float* mask, int mask_mode, void* stream) {
+    TP_REQUIRE(qt && h2k && h2v && mr_k && mr_v && u, "tp_test_region_attention_absorbed: NULL argument");
+    TP_REQUIRE(al16(qt) && al16(h2k) && al16(h2v) && al16(u), "tp_test_region_attention_absorbed: qt / h2k / h2v / u must be 16-byte aligned");
+    TP_REQUIRE(((uintptr_t)mr_k & 7) == 0 && ((uintptr_t)mr_v & 7) == 0, "tp_test_region_attention_absorbed: mr_k / mr_v must be 8-byte aligned");
+    TP_TRY(attention_geometry("tp_test_region_attention_absorbed", B, grid, s, mask, mask_mode));
+    return region_attention_absorbed_launch(qt, h2k, h2v, mr_k, mr_v, u, B, grid, s, (hipStream_t)stream, mask, mask_mode);   // (refuses s*s > 64)
+}
+
 // ---- the backward's kernels, one launcher each (tp_internal.h: bw_*_launch, point_queries_bwd_launch, gemm_launch) -------------
 
 int tp_test_bw_transpose(int src_dtype, int dst_dtype, const void* src, int64_t ld, int rows_per_batch, int64_t batch_stride,
