@@ -111,6 +111,40 @@ int tp_test_point_queries_bwd(int dtype, const float* dq0, const float* inv_scal
 int tp_test_linear_bwd(int M, int N, int K, int dtype, int out_dtype, int flags, const void* A, int64_t lda, const void* W, void* C,
                        int64_t ldc, const void* Z, int64_t ldz, const float* out_scale, int tile, void* stream);
 
+/* ---- test hooks: the weight-gradient contraction dW [n_out, k_in] = dY^T · X over `rows` token rows, as tp_backward launches it
+ * (tests/test_gpu_wgrad_edges.py).  The public tp_wgrad fixes half of the launchers' options; these do not. */
+
+/* Host logic only, no GPU needed: the split the launchers would use for this shape — *splits = S groups of *rows_per_split = Ks
+ * contraction rows each (Ks a multiple of 64; S * n_out * k_in * 4 bytes of `part` are written).  It CALLS the launchers' rule
+ * (csrc/tp_internal.h: wgrad_plan), it is no copy of it.  transposed 0: the in-place form (rpad ignored); 1: the transposed form,
+ * whose split follows rpad (a multiple of 1024, >= rows).  rows > 0, n_out % 8 == 0, k_in % 256 == 0, else TP_ERR_INVALID_ARG. */
+int tp_test_wgrad_plan(int64_t rows, int n_out, int k_in, int transposed, int64_t rpad, int* splits, long long* rows_per_split);
+
+/* Pass-through to wgrad_tt_launch (transposed 0) / wgrad_tn_launch (transposed 1): same objects, same kernels as tp_backward.
+ *   dy [rows, ldy] (dtype), read in place; only columns 0 .. n_out - 1 of rows 0 .. rows - 1 may reach the result.
+ *   transposed 0:  x [rows, ldx] (dtype) read in place; row r lives at x + (r / rows_per_batch) batch_stride + (r % rows_per_batch)
+ *       ldx (rows_per_batch 0 or >= rows: contiguous; else a multiple of 64, >= 128 — the launcher refuses others).  OR the four
+ *       x_part pointers with x NULL: k_in = 4 n_part columns from four tensors with the same ldx / rows_per_batch / batch_stride.
+ *   transposed 1:  x = X^T [k_in, ldx] with ldx = rpad (a multiple of 1024, >= rows) and ZEROS in columns rows .. rpad - 1 (the
+ *       caller's contract); no parts, no rows_per_batch / batch_stride, no split_row.
+ *   grad_out (out_dtype: TP_BF16 / TP_F16 / TP_F32) = cast(out_scale[0] * dW) (out_scale: device fp32, optional), added to what
+ *       grad_out holds when accumulate = 1 (TP_F32 only).  0 < split_row < n_out: rows [0, split_row) of dW go to grad_out, rows
+ *       [split_row, n_out) to grad_out_hi; either side (not both) may be NULL — it is not reduced and nothing is written through it.
+ *   counters (optional): ONE tile-queue slot as tp_backward hands one to every launch — `counter_ints` >= 32 device ints
+ *       ([4 groups][8 XCDs] queue heads), ZEROED by the caller before EVERY launch (the launch leaves its draws in them).  The
+ *       launchers pass the slot on only when S <= 4; with more splits it is ignored and comes back untouched.
+ *   part: `part_bytes` >= S * n_out * k_in * 4 (tp_wgrad_workspace_bytes always suffices), 256-byte aligned; all of it is scratch.
+ * Checked on the host before anything is enqueued (TP_ERR_INVALID_ARG, tp_last_error() says why): NULL pointers, 16-byte alignment
+ * of dy / x / parts / grad_out / grad_out_hi (256 of part, 4 of out_scale / counters), accumulate with a 16-bit out_dtype, parts /
+ * split_row / batch strides together with the transposed form, ldy < n_out, strides shorter than a row.  Shapes the launchers
+ * themselves refuse (k_in % 256, n_out % 8, strides % 8, rows_per_batch) come back with the launcher's message ("tp wgrad: ..."),
+ * a part too small with TP_ERR_WORKSPACE. */
+int tp_test_wgrad(const void* dy, int64_t ldy, const void* x, int64_t ldx, int rows_per_batch, int64_t batch_stride,
+                  const void* x_part0, const void* x_part1, const void* x_part2, const void* x_part3, int n_part,
+                  int64_t rows, int n_out, int k_in, int dtype, int out_dtype, void* grad_out, void* grad_out_hi, int split_row,
+                  const float* out_scale, int accumulate, int* counters, size_t counter_ints, void* part, size_t part_bytes,
+                  int transposed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

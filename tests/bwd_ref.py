@@ -344,3 +344,49 @@ def gelu_z(M: int, N: int, seed: int, device="cpu"):
     for i in range(len(GELU_Z_SPECIALS)):
         z[:, (7 * i + 3) % N] = sp[i]
     return z
+
+
+# ---- the weight-gradient contraction dW = dY^T · X (tests/test_gpu_wgrad_edges.py) ---------------------------------------------------
+WGRAD_FAMILIES = ("ints", "gauss")
+WGRAD_TOL = {torch.float32: 1e-5, torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}      # max-norm error / max|ref|, by OUTPUT dtype
+WGRAD_DIGITS = 7                                 # at most this many base-5 digits of the row number are stamped into x: 78125 rows
+
+
+def wgrad_ref(dy: torch.Tensor, x: torch.Tensor, rows: int, chunk: int = 4608) -> torch.Tensor:
+    """dW [n_out, k_in] = dy[:rows]^T · x[:rows] in float64 on the rounded operands (row chunks keep the widened copies small).
+    Rows at and beyond `rows` are never touched: they may hold anything."""
+    ref = torch.zeros(dy.shape[1], x.shape[1], dtype=torch.float64, device=dy.device)
+    for r0 in range(0, rows, chunk):
+        r1 = min(rows, r0 + chunk)
+        ref += dy[r0:r1].double().t() @ x[r0:r1].double()
+    return ref
+
+
+def wgrad_operands(family: str, rows: int, n_out: int, k_in: int, dtype, seed: int, device="cpu"):
+    """(dy [rows, n_out], x [rows, k_in]) of one weight-gradient case, rounded to `dtype`.
+      gauss: N(0, 1).
+      ints:  seeded integers in [-2, 2] (exact in bf16 and fp16), made row-dependent: dy[:, 0] = x[:, 0] = 1 and x[r, 1..] = the
+             base-5 digits of r, minus 2 (as many digits as `rows` needs — a digit that never left 0 would be a constant column,
+             whose sums grow like 2 * rows towards fp16's range).  dy_r (x) x_r = dy_s (x) x_s then forces dy_r = dy_s (column 0 of x), x_r = x_s (column 0 of
+             dy) and r = s (the digits): no two token rows contribute the same outer product, so a row that is dropped, counted
+             twice or paired with another row's partner changes the exact result.  Every product is an integer of magnitude <= 4 and
+             every partial sum one below 4 * rows < 2^24 (rows < 2^22): fp32 accumulation is EXACT in any order, the fp32 result
+             equals the float64 reference bit for bit, a 16-bit result equals its one rounding."""
+    g = _gen(seed, device)
+    if family == "gauss":
+        dy = torch.randn(rows, n_out, generator=g, device=device)
+        x = torch.randn(rows, k_in, generator=g, device=device)
+    elif family == "ints":
+        assert rows < 5 ** WGRAD_DIGITS and k_in > WGRAD_DIGITS
+        dy = torch.randint(-2, 3, (rows, n_out), generator=g, device=device).float()
+        x = torch.randint(-2, 3, (rows, k_in), generator=g, device=device).float()
+        r = torch.arange(rows, device=device)
+        dy[:, 0] = 1.0
+        x[:, 0] = 1.0
+        d = 0
+        while d == 0 or 5 ** d < rows:
+            x[:, 1 + d] = ((r // 5 ** d) % 5 - 2).float()
+            d += 1
+    else:
+        raise ValueError(family)
+    return dy.to(dtype), x.to(dtype)

@@ -76,6 +76,9 @@ def test_wgrad_is_deterministic_and_rejects_bad_shapes():
     a = _wgrad(dy, x, 3000, 512, 768, torch.float32)
     b = _wgrad(dy, x, 3000, 512, 768, torch.float32)
     assert torch.equal(a, b)
+    ref = dy.double().t() @ x.double()                   # (ragged rows over four splits: 696 of the last split's 768 rows)
+    err = float((a.double() - ref).abs().max() / ref.abs().max())
+    assert err <= 1e-5, err
     ws = torch.empty(lib.tp_wgrad_workspace_bytes(512, 200), dtype=torch.uint8, device="cuda")
     rc = lib.tp_wgrad(dy.data_ptr(), 512, x.data_ptr(), 768, 0, 0, 3000, 512, 200, _capi.TP_BF16, a.data_ptr(), _capi.TP_F32,
                       0, ws.data_ptr(), ws.numel(), None)

@@ -76,7 +76,9 @@ TEST_SYMBOLS = ("tp_test_occupy_cus", "tp_test_pair_occupancy", "tp_test_gemm_ro
                 "tp_test_bw_reduce_many_parts", "tp_test_bw_dynamic_scale", "tp_test_bw_scale_cast", "tp_test_bw_ln_backward",
                 "tp_test_bw_region_attention", "tp_test_point_queries_bwd", "tp_test_linear_bwd",
                 # the forward's two attention kernels with a mask (tests/test_gpu_attention_masks.py)
-                "tp_test_region_attention", "tp_test_region_attention_absorbed")
+                "tp_test_region_attention", "tp_test_region_attention_absorbed",
+                # the weight-gradient contraction with every option of its launchers, and their split rule (tests/test_gpu_wgrad_edges.py)
+                "tp_test_wgrad", "tp_test_wgrad_plan")
 TP_COUNTER_SIDE_STREAMS, TP_COUNTER_PAIR_LAUNCHES = 0, 1
 EXP_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtokenpacker_exp.so")
 
@@ -443,7 +445,12 @@ def load_test_library(path: str = EXP_LIB_PATH) -> ctypes.CDLL:
             ("tp_test_point_queries_bwd", [c_int, v, v, v, c_int, c_int, c_int, v]),
             ("tp_test_region_attention", [v, v, v, v, c_int, c_int, c_int, v, c_int, c_int, v]),
             ("tp_test_region_attention_absorbed", [v, v, v, v, v, v, c_int, c_int, c_int, v, c_int, v]),
-            ("tp_test_linear_bwd", [c_int, c_int, c_int, c_int, c_int, c_int, v, c_int64, v, v, c_int64, v, c_int64, v, c_int, v])):
+            ("tp_test_linear_bwd", [c_int, c_int, c_int, c_int, c_int, c_int, v, c_int64, v, v, c_int64, v, c_int64, v, c_int, v]),
+            ("tp_test_wgrad_plan", [c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int), POINTER(ctypes.c_longlong)]),
+            # (dy, ldy, x, ldx, rows_per_batch, batch_stride, x_part0..3, n_part, rows, n_out, k_in, dtype, out_dtype, grad_out,
+            #  grad_out_hi, split_row, out_scale, accumulate, counters, counter_ints, part, part_bytes, transposed, stream)
+            ("tp_test_wgrad", [v, c_int64, v, c_int64, c_int, c_int64, v, v, v, v, c_int, c_int64, c_int, c_int, c_int, c_int, v, v,
+                               c_int, v, c_int, v, c_size_t, v, c_size_t, c_int, v])):
         fn = getattr(lib, name)
         fn.restype = c_int
         fn.argtypes = argtypes

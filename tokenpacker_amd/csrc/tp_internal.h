@@ -459,6 +459,9 @@ int wgrad_tt_launch(int dtype, const void* dY, long long ldy, const WgradX& X, l
                     float* part, size_t part_bytes, int out_dtype, void* grad_out, int* counters, hipStream_t stream,
                     void* grad_out_hi = nullptr, int split_row = 0, const float* out_scale = nullptr, bool accumulate = false);
 size_t wgrad_tt_part_bytes(int Nout, int Kin);
+// The split both launchers use (host logic only): *S groups of *Ks contraction rows (a multiple of 64) each.  `transposed`: the
+// wgrad_tn_launch form, whose rule reads `rpad`; otherwise wgrad_tt_launch's, which reads R.  Shapes as the launchers accept them.
+void wgrad_plan(long long R, int Nout, int Kin, bool transposed, long long rpad, int* S, long long* Ks);
 int wgrad_tn_launch(int dtype, const void* dY, long long ldy, const void* XT, long long rpad, long long R, int Nout, int Kin,
                     float* part, size_t part_bytes, int out_dtype, void* grad_out, int* counters, hipStream_t stream,
                     const float* out_scale = nullptr, bool accumulate = false);

@@ -232,4 +232,61 @@ int tp_test_linear_bwd(int M, int N, int K, int dtype, int out_dtype, int flags,
     return gemm_launch(dtype, out_dtype, g, (hipStream_t)stream);
 }
 
+// ---- the weight-gradient contraction dW = dY^T · X (tp_internal.h: wgrad_tt_launch, wgrad_tn_launch, wgrad_plan) ------------------
+
+int tp_test_wgrad_plan(int64_t rows, int n_out, int k_in, int transposed, int64_t rpad, int* splits, long long* rows_per_split) {
+    TP_REQUIRE(splits && rows_per_split, "tp_test_wgrad_plan: NULL argument");
+    TP_REQUIRE(transposed == 0 || transposed == 1, "tp_test_wgrad_plan: transposed 0 / 1");
+    TP_REQUIRE(rows > 0 && n_out > 0 && k_in > 0 && n_out % 8 == 0 && k_in % 256 == 0,
+               "tp_test_wgrad_plan: need rows > 0, n_out %% 8 == 0, k_in %% 256 == 0");
+    if (transposed) TP_REQUIRE(rpad % 1024 == 0 && rpad >= rows, "tp_test_wgrad_plan: the transposed form needs rpad %% 1024 == 0, rpad >= rows");
+    wgrad_plan(rows, n_out, k_in, transposed != 0, rpad, splits, rows_per_split);
+    return TP_OK;
+}
+
+int tp_test_wgrad(const void* dy, int64_t ldy, const void* x, int64_t ldx, int rows_per_batch, int64_t batch_stride,
+                  const void* x_part0, const void* x_part1, const void* x_part2, const void* x_part3, int n_part,
+                  int64_t rows, int n_out, int k_in, int dtype, int out_dtype, void* grad_out, void* grad_out_hi, int split_row,
+                  const float* out_scale, int accumulate, int* counters, size_t counter_ints, void* part, size_t part_bytes,
+                  int transposed, void* stream) {
+    const void* parts[4] = {x_part0, x_part1, x_part2, x_part3};
+    const bool any_part = x_part0 || x_part1 || x_part2 || x_part3 || n_part != 0;
+    TP_REQUIRE(transposed == 0 || transposed == 1, "tp_test_wgrad: transposed 0 / 1");
+    TP_REQUIRE(half_dtype(dtype) && any_dtype(out_dtype), "tp_test_wgrad: dtype must be TP_BF16 / TP_F16, out_dtype one of the three");
+    TP_REQUIRE(accumulate == 0 || accumulate == 1, "tp_test_wgrad: accumulate 0 / 1");
+    TP_REQUIRE(!accumulate || out_dtype == TP_F32, "tp_test_wgrad: accumulate needs an fp32 output (out_dtype %d)", out_dtype);
+    TP_REQUIRE(!(transposed && any_part), "tp_test_wgrad: the transposed form takes one X^T, not four parts");
+    TP_REQUIRE(!(transposed && split_row != 0), "tp_test_wgrad: the transposed form has no split_row / grad_out_hi");
+    TP_REQUIRE(!(transposed && grad_out_hi), "tp_test_wgrad: the transposed form has no split_row / grad_out_hi");
+    TP_REQUIRE(!(transposed && (rows_per_batch != 0 || batch_stride != 0)), "tp_test_wgrad: the transposed form has no batch stride");
+    TP_REQUIRE(dy && part, "tp_test_wgrad: NULL argument (dy / part)");
+    if (any_part) {
+        TP_REQUIRE(x_part0 && x_part1 && x_part2 && x_part3 && !x, "tp_test_wgrad: NULL argument (parts: all four, and x NULL)");
+        TP_REQUIRE(n_part > 0, "tp_test_wgrad: parts need n_part > 0");
+        TP_REQUIRE(al16(x_part0) && al16(x_part1) && al16(x_part2) && al16(x_part3), "tp_test_wgrad: the x parts must be 16-byte aligned");
+    } else {
+        TP_REQUIRE(x, "tp_test_wgrad: NULL argument (x)");
+    }
+    TP_REQUIRE(rows > 0 && n_out > 0 && k_in > 0, "tp_test_wgrad: need rows, n_out, k_in > 0");
+    TP_REQUIRE(split_row >= 0 && split_row < n_out, "tp_test_wgrad: split_row must lie in [0, n_out)");
+    if (split_row > 0) TP_REQUIRE(grad_out || grad_out_hi, "tp_test_wgrad: NULL argument (grad_out and grad_out_hi)");
+    else TP_REQUIRE(grad_out && !grad_out_hi, "tp_test_wgrad: NULL argument (grad_out), or grad_out_hi without a split_row");
+    TP_REQUIRE(al16(dy) && al16(x) && al16(grad_out) && al16(grad_out_hi), "tp_test_wgrad: dy / x / grad_out / grad_out_hi must be 16-byte aligned");
+    TP_REQUIRE(((uintptr_t)part & 255) == 0, "tp_test_wgrad: part must be 256-byte aligned");
+    TP_REQUIRE(((uintptr_t)out_scale & 3) == 0 && ((uintptr_t)counters & 3) == 0, "tp_test_wgrad: out_scale / counters must be 4-byte aligned");
+    TP_REQUIRE(!counters || counter_ints >= 32, "tp_test_wgrad: a counters slot is 32 zeroed ints ([4 groups][8 XCDs])");
+    TP_REQUIRE(ldy >= n_out, "tp_test_wgrad: ldy < n_out");
+    if (transposed) {
+        TP_REQUIRE(ldx >= rows, "tp_test_wgrad: the transposed form needs ldx (= rpad) >= rows");
+        return wgrad_tn_launch(dtype, dy, ldy, x, ldx, rows, n_out, k_in, (float*)part, part_bytes, out_dtype, grad_out, counters,
+                               (hipStream_t)stream, out_scale, accumulate != 0);
+    }
+    TP_REQUIRE(ldx >= (any_part ? n_part : k_in), "tp_test_wgrad: ldx is shorter than a row of x");
+    if (rows_per_batch > 0 && rows_per_batch < rows)
+        TP_REQUIRE(batch_stride >= (int64_t)rows_per_batch * ldx, "tp_test_wgrad: batch_stride must cover rows_per_batch rows");
+    const WgradX X{any_part ? x_part0 : x, ldx, rows_per_batch, batch_stride, any_part ? parts : nullptr, any_part ? n_part : 0};
+    return wgrad_tt_launch(dtype, dy, ldy, X, rows, n_out, k_in, (float*)part, part_bytes, out_dtype, grad_out, counters,
+                           (hipStream_t)stream, grad_out_hi, split_row, out_scale, accumulate != 0);
+}
+
 }  // extern "C"

@@ -126,11 +126,27 @@ static BwLayout bw_layout(int B, int grid, int s, int D, bool f16_chain, bool in
 #define TP_TRY(expr) do { int rc_ = (expr); if (rc_ != TP_OK) return rc_; } while (0)
 
 // ---- weight gradients from K-major operands ---------------------------------------------------------------------
-static int wgrad_splits(long long R, int Nout, int Kin) {
+// The split rule of both forms, in ONE place (tp_test_wgrad_plan reports it; the launchers below use nothing else): S groups of
+// Ks contraction rows each, Ks whole K-tiles, S * tiles(256^2) <= ~256 workgroups.
+//   in place:    S doubles while a split keeps >= 512 rows; Ks = ceil64(ceil(R / S)).  Rounding Ks up to whole K-tiles can push
+//                the LAST split past R altogether (S = 16 only: R = 8193 gives Ks = 576 and 15 * 576 >= R) — a group of
+//                workgroups and a partial that hold nothing but masked rows; S is halved until every split owns a row.
+//   transposed:  S doubles while rpad / S stays a multiple of 64 and >= 256 columns; Ks = rpad / S (splits of nothing but the
+//                caller's zero padding are allowed: rpad is the caller's choice).
+void wgrad_plan(long long R, int Nout, int Kin, bool transposed, long long rpad, int* S_out, long long* Ks_out) {
     const long long tiles = (long long)((Nout + 255) / 256) * (Kin / 256);
     int S = 1;
-    while (S < 16 && tiles * S < 256 && R / (S * 2) >= 512) S *= 2;
-    return S;
+    long long Ks;
+    if (transposed) {
+        while (S < 16 && tiles * S < 256 && (rpad / (S * 2)) % 64 == 0 && rpad / (S * 2) >= 256) S *= 2;
+        Ks = rpad / S;
+    } else {
+        while (S < 16 && tiles * S < 256 && R / (S * 2) >= 512) S *= 2;
+        auto rows_per_split = [&](int s) { return ((R + s - 1) / s + 63) / 64 * 64; };
+        while (S > 1 && (S - 1) * rows_per_split(S) >= R) S /= 2;
+        Ks = rows_per_split(S);
+    }
+    *S_out = S; *Ks_out = Ks;
 }
 size_t wgrad_tt_part_bytes(int Nout, int Kin) { return (size_t)16 * Nout * Kin * 4; }
 
@@ -150,9 +166,9 @@ int wgrad_tt_launch(int dtype, const void* dY, long long ldy, const WgradX& X, l
                   R, Nout, Kin);
         return TP_ERR_INVALID_ARG;
     }
-    const int S = wgrad_splits(R, Nout, Kin);
+    int S; long long Ks;                                 // contraction rows per split: whole K-tiles
+    wgrad_plan(R, Nout, Kin, false, 0, &S, &Ks);
     if ((size_t)S * Nout * Kin * 4 > part_bytes) { set_error("tp wgrad: split partial buffer too small"); return TP_ERR_WORKSPACE; }
-    const long long Ks = ((R + S - 1) / S + 63) / 64 * 64;          // contraction rows per split, whole K-tiles
     GemmArgs a{};
     a.A = (const char*)dY; a.lda_bytes = ldy * 2; a.a_gs = Ks * ldy * 2;
     a.W = X.parts ? (const char*)X.parts[0] : (const char*)X.x; a.ldw_bytes = X.ldx * 2; a.w_gs = 0;
@@ -182,15 +198,13 @@ int wgrad_tt_launch(int dtype, const void* dY, long long ldy, const WgradX& X, l
 int wgrad_tn_launch(int dtype, const void* dY, long long ldy, const void* XT, long long rpad, long long R, int Nout, int Kin,
                     float* part, size_t part_bytes, int out_dtype, void* grad_out, int* counters, hipStream_t stream,
                     const float* out_scale, bool accumulate) {
-    if (R <= 0 || Nout <= 0 || Kin % 256 != 0 || Nout % 8 != 0 || ldy % 8 != 0 || rpad % 1024 != 0 || rpad < R) {
+    if (R <= 0 || Nout <= 0 || Kin <= 0 || Kin % 256 != 0 || Nout % 8 != 0 || ldy % 8 != 0 || rpad % 1024 != 0 || rpad < R) {
         set_error("tp wgrad: unsupported shape R=%lld rpad=%lld Nout=%d Kin=%d", R, rpad, Nout, Kin);
         return TP_ERR_INVALID_ARG;
     }
-    const long long tiles = (long long)((Nout + 255) / 256) * (Kin / 256);
-    int S = 1;
-    while (S < 16 && tiles * S < 256 && (rpad / (S * 2)) % 64 == 0 && rpad / (S * 2) >= 256) S *= 2;
+    int S; long long Ks;
+    wgrad_plan(R, Nout, Kin, true, rpad, &S, &Ks);
     if ((size_t)S * Nout * Kin * 4 > part_bytes) { set_error("tp wgrad: split partial buffer too small"); return TP_ERR_WORKSPACE; }
-    const long long Ks = rpad / S;
     GemmArgs a{};
     a.A = (const char*)dY; a.lda_bytes = ldy * 2; a.a_gs = Ks * ldy * 2;
     a.W = (const char*)XT; a.ldw_bytes = rpad * 2; a.w_gs = Ks * 2;
