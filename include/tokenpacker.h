@@ -46,6 +46,8 @@ extern "C" {
  * parameters that are their own masters).  Without the flag / with a 16-bit optimizer dtype nothing changes, bits included. */
 /* ABI 6, extended a fifth time (by symbol, the version stays 6): tp_optim_sumsq and tp_optim_apply — tp_optim_step cut in two with
  * room for a collective in between, for an optimizer whose state is sharded across ranks.  tp_optim_step is unchanged, bits included. */
+/* ABI 6, extended again (by symbol, the version stays 6): tp_shift_ce_args, tp_shift_ce_workspace_bytes, tp_shift_ce_forward and
+ * tp_shift_ce_backward — the LLM's shifted cross-entropy on given logits.  Nothing else changes. */
 #define TP_ABI_VERSION 6
 
 typedef enum tp_status {
@@ -703,6 +705,66 @@ typedef struct tp_splice_args {
 int tp_splice(const tp_splice_args* args, void* stream);
 size_t tp_splice_backward_workspace_bytes(int64_t n_feat_blocks, int M);
 int tp_splice_backward(const tp_splice_args* args, void* stream);
+
+/* ---- shifted cross-entropy over the labelled rows (ABI 6 extension) ------------------------------------------------------
+ * The loss of the reference's LLM wrapper on GIVEN logits (llava/model/language_model/llava_llama.py:95-106):
+ *     shift_logits = logits[..., :-1, :].contiguous();  shift_labels = labels[..., 1:].contiguous()
+ *     loss = CrossEntropyLoss()(shift_logits.view(-1, V), shift_labels.view(-1))
+ * without the shifted copy, the log-softmax and (in place) the gradient buffer, and without reading a row whose target is
+ * `ignore_index` — after the splice most rows are (images, separators, prompt, padding).  No GEMM is part of it.
+ *
+ * logits [batch, len, V], dtype TP_BF16 / TP_F16 / TP_F32, last-dimension stride 1, `row_stride` (>= V) and `batch_stride`
+ * (any value) in ELEMENTS: a padded-vocabulary view buf[..., :V] qualifies.  The base pointer and every row need only the
+ * alignment of one element; the kernels go element by element up to the first 16-byte boundary of a row and after its last
+ * whole 16-byte vector, and never access 16 bytes wide at another address.  All addressing is 64-bit (a 64-bit row base plus a
+ * 32-bit offset inside the row).  labels [batch, len] int64, contiguous.
+ *
+ * tp_shift_ce_forward: row (b, t), t < len - 1, has the target labels[b, t + 1].  One workgroup per row; a labelled row is
+ * read from memory once (online maximum and rescaled sum, fp32) and leaves lse, its loss -log_softmax(x)[target], its maximum
+ * and the log of its rescaled sum in the workspace.  A second launch of one workgroup sums the row losses (fp64) and counts
+ * the labelled rows in a fixed order, no atomics — two runs give the same bits — and writes, at the head of the workspace:
+ *     byte TP_SHIFT_CE_LOSS_OFFSET     float    sum / n_valid (TP_CE_MEAN, the reference's reduction) or sum (TP_CE_SUM)
+ *     byte TP_SHIFT_CE_INV_N_OFFSET    float    1 / n_valid
+ *     byte TP_SHIFT_CE_N_VALID_OFFSET  int64    n_valid, the rows whose target is not ignore_index
+ * followed at byte 256 by four fp32 arrays of batch * (len - 1) words, row b * (len - 1) + t: lse | loss | max | log(sum).
+ * tp_shift_ce_workspace_bytes(batch, len) = 256 + 16 * batch * (len - 1) rounded up to 256 (0 for sizes < 1).
+ *
+ * tp_shift_ce_backward (same struct, after the forward on the same workspace): one launch writes the whole of dlogits
+ * [batch, len, V] (d_row_stride, d_batch_stride, the logits' dtype):
+ *     dlogits[b, t, v] = g * w * (exp(x - lse) - [v == target]),   g = *grad_loss (read on the device),
+ *     w = 1 / n_valid (TP_CE_MEAN) or 1 (TP_CE_SUM),
+ * and zeros in every unlabelled row and in row len - 1 of every sample.  A labelled row is read once and written once.
+ * dlogits may equal logits (in place; the strides must then be equal).  Otherwise every dlogits row must sit at the same
+ * offset from a 16-byte boundary as its logits row: the base pointers and both pairs of strides congruent modulo 16 bytes.
+ *
+ * Non-finite inputs behave as F.cross_entropy on the logits upcast to fp32: no labelled row -> loss NaN (mean), gradient
+ * zero; -inf logits beside finite ones -> finite loss, exact zeros in the gradient; -inf at the target -> loss +inf, finite
+ * gradient; a row of -inf only -> NaN loss and NaN in that row's gradient.  A target outside [0, V) that is not
+ * ignore_index counts as labelled and makes its row's loss, hence the loss, NaN; its gradient row is zeros; no address is
+ * ever formed from a target and there is no device assert.
+ *
+ * Both calls validate on the host first (TP_ERR_INVALID_ARG: NULL pointers, an unknown dtype or reduction, V / len / batch
+ * < 1, a row stride below V, a workspace that is too small, a pointer not aligned to its element size — labels 8, workspace
+ * 16, grad_loss 4 bytes —, dlogits not congruent to logits), then only enqueue: no allocation, no synchronisation. */
+enum { TP_CE_MEAN = 0, TP_CE_SUM = 1 };
+#define TP_SHIFT_CE_LOSS_OFFSET 0
+#define TP_SHIFT_CE_INV_N_OFFSET 4
+#define TP_SHIFT_CE_N_VALID_OFFSET 8
+typedef struct tp_shift_ce_args {
+    int32_t batch, len, V, dtype, reduction, reserved;
+    int64_t row_stride, batch_stride;         /* logits, in elements */
+    int64_t d_row_stride, d_batch_stride;     /* dlogits, in elements (backward) */
+    int64_t ignore_index;
+    const void* logits;
+    const int64_t* labels;
+    void* workspace;
+    size_t workspace_bytes;
+    const float* grad_loss;                   /* backward: the incoming 0-dim fp32 gradient, on the device */
+    void* dlogits;                            /* backward */
+} tp_shift_ce_args;
+size_t tp_shift_ce_workspace_bytes(int batch, int len);
+int tp_shift_ce_forward(const tp_shift_ce_args* args, void* stream);
+int tp_shift_ce_backward(const tp_shift_ce_args* args, void* stream);
 
 /* ---- TokenPacker-HD image slicing (the step before the CLIP tower) ---------------------------------------------
  * Replaces the resize / zero-pad / tile code of the data loader and the eval drivers (llava/train/train.py:695-731):

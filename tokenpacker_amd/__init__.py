@@ -8,9 +8,11 @@ library; *using* the projector needs both.
 from .projector import TokenPacker, build_vision_projector  # noqa: F401
 from . import splice  # noqa: F401
 from .splice import build_multimodal_inputs, splice_layout  # noqa: F401
+from . import loss  # noqa: F401
+from .loss import shifted_cross_entropy  # noqa: F401
 from . import optim  # noqa: F401
 from .optim import MainGradAdamW, ShardedMainGradAdamW, shard_layout, shard_slices  # noqa: F401
 
-__all__ = ["TokenPacker", "build_vision_projector", "splice", "build_multimodal_inputs", "splice_layout", "optim",
+__all__ = ["TokenPacker", "build_vision_projector", "splice", "build_multimodal_inputs", "splice_layout", "loss", "shifted_cross_entropy", "optim",
            "MainGradAdamW", "ShardedMainGradAdamW", "shard_layout", "shard_slices"]
 __version__ = "0.1.0"

@@ -64,6 +64,7 @@ EXPORTED_SYMBOLS = (
     "tp_optim_workspace_bytes", "tp_optim_step", "tp_optim_sumsq", "tp_optim_apply",
     "tp_hd_assemble_backward_workspace_bytes", "tp_hd_assemble_backward",
     "tp_splice", "tp_splice_backward_workspace_bytes", "tp_splice_backward",
+    "tp_shift_ce_workspace_bytes", "tp_shift_ce_forward", "tp_shift_ce_backward",
     "tp_desc_known_flags", "tp_hd_slice_u8",
     "tp_resize_coeffs", "tp_clip_preprocess_workspace_bytes", "tp_clip_preprocess",
     "tp_tuning_create", "tp_tuning_destroy", "tp_tuning_set", "tp_tuning_get", "tp_gather_alloc_flags", "tp_gather_free_flags", "tp_gather_export", "tp_gather_open", "tp_gather_close", "tp_gather_push", "tp_gather_sync",
@@ -209,6 +210,19 @@ class tp_splice_args(Structure):
                 ("dout", c_void_p), ("dfeats", c_void_p), ("dtable", c_void_p),
                 ("padding_idx", c_int64), ("n_table_rows", c_int64),
                 ("order_host", c_void_p), ("order_dev", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t)]
+
+
+TP_CE_MEAN, TP_CE_SUM = 0, 1
+TP_SHIFT_CE_LOSS_OFFSET, TP_SHIFT_CE_INV_N_OFFSET, TP_SHIFT_CE_N_VALID_OFFSET = 0, 4, 8
+
+
+class tp_shift_ce_args(Structure):
+    """tp_shift_ce_forward / tp_shift_ce_backward (include/tokenpacker.h, "shifted cross-entropy"): one struct for both."""
+    _fields_ = [("batch", c_int32), ("len", c_int32), ("V", c_int32), ("dtype", c_int32), ("reduction", c_int32), ("reserved", c_int32),
+                ("row_stride", c_int64), ("batch_stride", c_int64), ("d_row_stride", c_int64), ("d_batch_stride", c_int64),
+                ("ignore_index", c_int64),
+                ("logits", c_void_p), ("labels", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t),
+                ("grad_loss", c_void_p), ("dlogits", c_void_p)]
 
 
 _lib = None
@@ -369,6 +383,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.tp_splice_backward_workspace_bytes.argtypes = [c_int64, c_int]
     lib.tp_splice_backward.restype = c_int
     lib.tp_splice_backward.argtypes = [POINTER(tp_splice_args), c_void_p]
+    lib.tp_shift_ce_workspace_bytes.restype = c_size_t
+    lib.tp_shift_ce_workspace_bytes.argtypes = [c_int, c_int]
+    lib.tp_shift_ce_forward.restype = c_int
+    lib.tp_shift_ce_forward.argtypes = [POINTER(tp_shift_ce_args), c_void_p]
+    lib.tp_shift_ce_backward.restype = c_int
+    lib.tp_shift_ce_backward.argtypes = [POINTER(tp_shift_ce_args), c_void_p]
 
     if hasattr(lib, "tp_optim_sumsq") and hasattr(lib, "tp_optim_apply"):     # (an ABI 6 extension — sharded_optim_supported())
         lib.tp_optim_sumsq.restype = c_int
